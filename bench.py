@@ -7,7 +7,12 @@ in HBM.  Default workload: BASELINE config 2 -- B = 1024 kinematic-bicycle
 problems, N = 20, fp64, per GPU.  With --gpus N under torchrun each rank solves
 its own batch (weak scaling, no data-path collective); rank 0 prints one JSON line.
 
-The same line carries, under "c3", BASELINE config 3 -- B = 4096 dynamic-bicycle
+A plain run does only that: set up, warm up, time the --steps steps, write the last step's
+outputs if --dump-outputs DIR is given (DIR/<name>.npy: u_star, xbar, u0, status, iters of rank 0,
+float64, at most 64 MB in all -- a fixed seeded sample of the rows, listed in rows.npy, above that),
+print the line.  Everything below is measured only with --full.
+
+With --full the same line carries, under "c3", BASELINE config 3 -- B = 4096 dynamic-bicycle
 (linear tyre) single-track NMPC problems per GPU, N = 40, 3 SQP iterations, solved in fp64
 (vc_solve on a dynamic context, csrc/st_sqp.hip: the kernel that meets the 1e-5 parity bar,
 and the faster one) -- measured the same way; it is a secondary workload, not `value`.
@@ -21,7 +26,11 @@ plant, all on the device, vc_simulate), vehicles sharded over the ranks.  Under
 config/controllers/cascaded.yaml), B = 4096 per GPU, fp64
 (csrc/casc_ric.hip, stagewise Riccati).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--c3-batch B3]
+With --full the headline line also carries its roofline block (one untimed diagnostic solve for the
+polish rounds), the host-pointer rate and the CPU baselines.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR]
+    python bench.py --full [--gpus N] [--steps K] [--warmup W] [--batch B] [--c3-batch B3]
                     [--c5-vehicles V] [--c5-steps S] [--no-c3] [--no-c5] [--no-cpu-baseline]
 """
 from __future__ import annotations
@@ -206,6 +215,13 @@ def parse():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=1024, help="problems per GPU (config 2: 1024)")
     ap.add_argument("--seed", type=int, default=31)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: its roofline block and host-pointer rate, the CPU baselines and "
+                         "every secondary leg (C4, kinematic legs, C3, cascaded, C5, latency); the --no-* and "
+                         "per-leg size options below act only with --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (rank 0's batch: u_star, xbar, "
+                         "u0, status, iters) as DIR/<name>.npy, float64, at most 64 MB in all")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample", type=int, default=1024, help="problems in the CPU-baseline sample")
     ap.add_argument("--c3-batch", type=int, default=4096, help="C3 problems per GPU (config 3: 4096)")
@@ -877,6 +893,27 @@ def run_latency(args, dev):
     return out
 
 
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(path, tensors):
+    """--dump-outputs: each device tensor ([B, ...], one row per problem) as path/<name>.npy in
+    float64.  Above DUMP_MAX_BYTES in all, the same fixed seeded sample of the rows of every array
+    (sorted, listed in rows.npy) is written, so two builds run with the same arguments write
+    comparable files."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrs = {k: v.detach().cpu().numpy().astype(np.float64) for k, v in tensors.items()}
+    B = len(next(iter(arrs.values())))
+    row_bytes = sum(a.nbytes for a in arrs.values()) // B + 8          # + the row's entry in rows.npy
+    if B * row_bytes > DUMP_MAX_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(B, DUMP_MAX_BYTES // row_bytes, replace=False))
+        arrs = {k: a[rows] for k, a in arrs.items()}
+        arrs["rows"] = rows.astype(np.float64)
+    for k, a in arrs.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a))
+
+
 def main():
     args = parse()
     from vcmpc import dist
@@ -944,6 +981,38 @@ def main():
     kern_ms = float(np.mean([a.elapsed_time(b) for a, b in events]))
     st = status.cpu().numpy()
     it = iters.cpu().numpy()
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step (the diagnostic solve of
+        # --full below overwrites these buffers)
+        dump_outputs(args.dump_outputs, {"u_star": t["ubar"], "xbar": xbar, "u0": u0, "status": status, "iters": iters})
+    solves, elapsed_max, kern_ms_max = dist.aggregate(float(B * args.steps), elapsed, kern_ms, dev)
+    head = {
+        "metric": "MPC solves/sec (batched, N=20)",
+        "value": solves / elapsed_max,
+        "unit": "solves/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed_max / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": ("synthetic (seeded C2 sampler, vcmpc/workload.py: SURVEY 8(d)'s x0 / kappa / ubar "
+                 "distributions; per-stage ds_n = 0.03 vbar_n + 0.5 from the warm start's speed "
+                 "prediction, kinematic_mpc.py:178-182; problems whose warm-start rollout drops to "
+                 "v <= 1 m/s or reaches |epsi| >= 1.2 rad are re-drawn)"),
+        "config": {"workload": f"C2 kinematic-bicycle LTV-MPC, B={B} per GPU, N={N_HORIZON}, fp64",
+                   "batch_per_gpu": B, "global_batch": B * world, "horizon": N_HORIZON,
+                   "parallelism": f"dp{world} (independent shards)"},
+    }
+    solver_stats = {"solved_frac": float((st == 0).mean()), "iters_mean": float(it.mean()), "iters_max": int(it.max())}
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(dict(head, kernel="kin_ltv_kernel<20>", kernel_ms=kern_ms, solver=solver_stats)), flush=True)
+        ctx.close()
+        dist.shutdown()
+        return
     # polish rounds per problem (untimed diagnostic call on the same problems): each round is a
     # normal-matrix build + factorisation + solves, the work of one interior-point iteration
     t["ubar"].copy_(ubar0)
@@ -959,7 +1028,6 @@ def main():
     for _ in range(reps):
         ctx.solve(host["x0"], host["kappa"], host["ds"], host["ubar"].copy())
     host_rate = B * reps / (time.perf_counter() - th)
-    solves, elapsed_max, kern_ms_max = dist.aggregate(float(B * args.steps), elapsed, kern_ms, dev)
     c4 = None
     if not args.no_c4:
         try:
@@ -1042,29 +1110,11 @@ def main():
         lat = run_latency(args, dev)
 
     if rank == 0:
-        value = solves / elapsed_max
         achieved = BYTES_PER_SOLVE * B / (kern_ms / 1e3) / 1e9
         flops = FLOP_SWEEP + (float(it.mean()) + polish_rounds) * FLOP_ITER  # + the polish rounds
         flops_F = 0.42e6 + (float(it.mean()) + polish_rounds) * 0.28e6
         out = {
-            "metric": "MPC solves/sec (batched, N=20)",
-            "value": value,
-            "unit": "solves/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed_max / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": ("synthetic (seeded C2 sampler, vcmpc/workload.py: SURVEY 8(d)'s x0 / kappa / ubar "
-                     "distributions; per-stage ds_n = 0.03 vbar_n + 0.5 from the warm start's speed "
-                     "prediction, kinematic_mpc.py:178-182; problems whose warm-start rollout drops to "
-                     "v <= 1 m/s or reaches |epsi| >= 1.2 rad are re-drawn)"),
-            "config": {"workload": f"C2 kinematic-bicycle LTV-MPC, B={B} per GPU, N={N_HORIZON}, fp64",
-                       "batch_per_gpu": B, "global_batch": B * world, "horizon": N_HORIZON,
-                       "parallelism": f"dp{world} (independent shards)"},
+            **head,
             # the binding roofline is fp64 compute ("not HBM").  The kernel's fp64 work
             # splits between the VALU and the matrix cores: the v_mfma_f64_16x16x4_f64 tiles (the
             # normal-matrix build C'DC and the blocked factorisation's trailing updates) execute
@@ -1093,8 +1143,7 @@ def main():
                                  "frac": achieved / HBM_PEAK_GBS, "algorithmic_bytes": BYTES_PER_SOLVE * B,
                                  "bytes_per_solve": BYTES_PER_SOLVE}},
             "host_ptr_solves_per_s": host_rate,
-            "solver": {"solved_frac": float((st == 0).mean()), "iters_mean": float(it.mean()),
-                       "iters_max": int(it.max())},
+            "solver": solver_stats,
         }
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(data, min(args.cpu_sample, B))

@@ -11,11 +11,11 @@ OUT=$ROOT/gpurun_out
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd "$ROOT"
-timeout -k 10 600 python bench.py --steps 20 --warmup 3 > "$OUT/bench_$TAG.log" 2>&1
+timeout -k 10 600 python bench.py --full --steps 20 --warmup 3 > "$OUT/bench_$TAG.log" 2>&1
 rc=$?; echo "bench rc=$rc"; [ $rc -ge 124 ] && exit $rc
 cd /tmp
 timeout -k 10 600 rocprofv3 --kernel-trace --marker-trace --stats -f csv -d "$OUT/prof_$TAG" -o run -- \
-    python3 "$ROOT/bench.py" --steps 20 --warmup 3 --no-cpu-baseline --no-latency > "$OUT/rocprof_$TAG.log" 2>&1
+    python3 "$ROOT/bench.py" --full --steps 20 --warmup 3 --no-cpu-baseline --no-latency > "$OUT/rocprof_$TAG.log" 2>&1
 rc=$?; echo "rocprof rc=$rc"; [ $rc -ge 124 ] && exit $rc
 cd "$ROOT"
 python scripts/leg_stats.py "$OUT/prof_$TAG" > "$OUT/kernel_leg_stats_$TAG.csv"

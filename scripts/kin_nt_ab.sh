@@ -6,7 +6,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/ntab_$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-LEGS="--no-c3 --no-c4 --no-c5 --no-casc --no-kin-legs --no-latency --no-cpu-baseline"
+LEGS="--full --no-c3 --no-c4 --no-c5 --no-casc --no-kin-legs --no-latency --no-cpu-baseline"
 for v in default nt; do
   unset VCMPC_LIB
   [ "$v" != default ] && export VCMPC_LIB="$ROOT/vehicle-control_amd/vcmpc/libvcmpc_$v.so"

@@ -10,7 +10,7 @@ TAG=$1
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/kinocc_$TAG
 mkdir -p "$OUT"
-LEGS="--no-c3 --no-c4 --no-c5 --no-casc --no-kin-legs --no-latency --no-cpu-baseline"
+LEGS="--full --no-c3 --no-c4 --no-c5 --no-casc --no-kin-legs --no-latency --no-cpu-baseline"
 for B in 256 512 1024 1536 2048 4096 8192 65536; do
   timeout -k 10 300 python "$ROOT/bench.py" --batch $B $LEGS > "$OUT/b$B.log" 2>&1 || exit $?
 done

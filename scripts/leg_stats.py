@@ -8,8 +8,8 @@ and end inside the range's host timestamps, same clock in rocprofv3's traces) an
 per (leg, kernel).  bench.py's `kernel_ms` of a leg is the mean HIP-event time of its timed
 launches and must match the AverageNs of its row.
 
-    rocprofv3 --kernel-trace --marker-trace --stats -f csv -d gpurun_out/prof_<tag> -o run -- python3 bench.py ...
-    python scripts/leg_stats.py gpurun_out/prof_<tag> > profiles/<round>/kernel_leg_stats_<tag>.csv
+    rocprofv3 --kernel-trace --marker-trace --stats -f csv -d <dir>/prof_<tag> -o run -- python3 bench.py --full ...
+    python scripts/leg_stats.py <dir>/prof_<tag> > profiles/<round>/kernel_leg_stats_<tag>.csv
 """
 import collections
 import csv

@@ -1,5 +1,5 @@
 """Open-loop replay of the reference's recorded closed-loop runs through the drop-in
-controllers (tests/golden/replay_kat.npz, make_replay_kat.py): at every recorded control step
+controllers (tests/golden/replay_kat/, make_replay_kat.py): at every recorded control step
 the controller gets the recorded state (and its own previous solution as the unshifted warm
 start, as the reference's controller does), and its first input is compared with the input
 IPOPT computed there (action_traj[n + 1]: racing.py:77-84 logs a zero action first and then
@@ -20,6 +20,24 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "vehicle-control_amd")]
+
+
+def load_kat():
+    """The recorded runs of tests/golden/replay_kat/ (one .npz per run x controller key, each below
+    the repository's 1 MiB file limit; make_replay_kat.py) as one dict: "<key>/state_traj",
+    "<key>/action_traj", "<key>/preds" per key, and "configs" (JSON of every key's recorded config)."""
+    d = os.path.join(ROOT, "tests", "golden", "replay_kat")
+    out, cfgs = {}, {}
+    for fn in sorted(os.listdir(d)):
+        if not fn.endswith(".npz"):
+            continue
+        k = fn[:-4].replace("__", ":")
+        with np.load(os.path.join(d, fn), allow_pickle=False) as g:
+            for name in ("state_traj", "action_traj", "preds"):
+                out[f"{k}/{name}"] = g[name]
+            cfgs[k] = json.loads(str(g["config"]))
+    out["configs"] = np.array(json.dumps(cfgs))
+    return out
 
 
 def track_of(run):
@@ -122,7 +140,7 @@ def main():
     ap.add_argument("--inside", action="store_true", help="the reference's barrier inside obstacles (vc_obstacles.inside)")
     ap.add_argument("--table", action="store_true", help="print a markdown table of the results at the end")
     args = ap.parse_args()
-    g = dict(np.load(os.path.join(ROOT, "tests", "golden", "replay_kat.npz"), allow_pickle=False))
+    g = load_kat()
     recs = json.loads(str(g["configs"]))
     res = []
     for run in (sorted(recs) if args.runs == ["all"] else args.runs):

@@ -31,7 +31,7 @@ def main():
     import replay_recorded as R
     from vcmpc import solver
 
-    g = dict(np.load(os.path.join(ROOT, "tests", "golden", "replay_kat.npz"), allow_pickle=False))
+    g = R.load_kat()
     recs = json.loads(str(g["configs"]))
     events, absurd, calls = [], [], {"n": 0}
     orig = solver.Context.solve

@@ -1,4 +1,5 @@
-"""Generate tests/golden/replay_kat.npz: the reference's recorded closed-loop runs at the
+"""Generate tests/golden/replay_kat/<key>.npz (read back as one dict by
+scripts/replay_recorded.py load_kat()): the reference's recorded closed-loop runs at the
 controller shapes this build solves, for the open-loop *replay* test (tests/test_gpu_replay.py):
 the recorded state at every control step, the action IPOPT applied there and its predicted
 plan (get_state_prediction(), global x, y, psi per stage; simulation/racing.py:239-240,446).
@@ -62,7 +63,7 @@ def key(run, ctl):
 
 
 def main():
-    out, cfgs = {}, {}
+    os.makedirs(os.path.join(HERE, "replay_kat"), exist_ok=True)
     for run, ctl in RUNS:
         d = os.path.join(DATA, run)
         x = np.load(os.path.join(d, f"{ctl}_state_traj.npy"), allow_pickle=False)
@@ -70,13 +71,13 @@ def main():
         p = np.load(os.path.join(d, f"{ctl}_preds.npy"), allow_pickle=False)
         k = key(run, ctl)
         with open(os.path.join(d, f"{ctl}_config.yaml")) as f:
-            cfgs[k] = yaml.safe_load(f)
-        out[f"{k}/state_traj"] = x
-        out[f"{k}/action_traj"] = u
-        out[f"{k}/preds"] = p[:, :, :2].astype(np.float32)   # global x, y per stage (plots-grade)
-    out["configs"] = np.array(json.dumps(cfgs))
-    np.savez_compressed(os.path.join(HERE, "replay_kat.npz"), **out)
-    print({k: v.shape for k, v in out.items()})
+            cfg = yaml.safe_load(f)
+        out = {"state_traj": x, "action_traj": u,
+               "preds": p[:, :, :2].astype(np.float32),   # global x, y per stage (plots-grade)
+               "config": np.array(json.dumps(cfg))}
+        # one file per key (":" -> "__" in the name): each stays below the 1 MiB file limit
+        np.savez_compressed(os.path.join(HERE, "replay_kat", k.replace(":", "__") + ".npz"), **out)
+        print(k, {n: v.shape for n, v in out.items()})
 
 
 if __name__ == "__main__":

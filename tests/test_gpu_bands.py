@@ -198,7 +198,8 @@ def test_recorded_obstacle_and_shoe_runs_within_bands(key):
         # closed_loop_cost): which closed loop is better by the reference's objective
         from oracle import dyn_sqp as D
         from oracle import models as M
-        g = np.load(os.path.join(GOLDEN, "replay_kat.npz"))
+        from replay_recorded import load_kat
+        g = load_kat()
         if f"{key}/state_traj" in g:
             p = M.dyn_params_from_config(load_config("dynamic_car"))
             W = D.dyn_weights(cfg)

@@ -1,5 +1,5 @@
 """GPU: the build's SQP against the reference's own IPOPT solutions.  Open-loop replay of
-recorded closed-loop runs (tests/golden/replay_kat.npz, make_replay_kat.py): at every
+recorded closed-loop runs (tests/golden/replay_kat/, make_replay_kat.py): at every
 recorded control step the drop-in controller gets the recorded state (its own previous
 solution as the unshifted warm start, cascaded_mpc.py:320-321), and its first input is
 compared with the command IPOPT produced from that state (action_traj[n + 1]: racing.py:77-84
@@ -26,12 +26,13 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture(scope="module")
 def data():
-    return dict(np.load(os.path.join(GOLDEN, "replay_kat.npz"), allow_pickle=False))
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(GOLDEN), "..", "scripts"))
+    from replay_recorded import load_kat
+    return load_kat()
 
 
 def _replay(data, run, sqp, qp=None):
-    import sys
-    sys.path.insert(0, os.path.join(os.path.dirname(GOLDEN), "..", "scripts"))
     from replay_recorded import replay
     recs = json.loads(str(data["configs"]))
     return replay(run, data, recs[run], sqp, qp=qp)
