@@ -49,7 +49,8 @@
  *     returns immediately; call vc_synchronize() before reading results.
  *   - Return value: 0 on success, a negative VC_E* code on an API or HIP error
  *     (message via vc_last_error).  Per-problem outcomes are reported in status[b]
- *     (VC_SOLVED, VC_MAX_ITER, VC_NONFINITE, VC_OUT_OF_DOMAIN); no exception-style failure, unlike the
+ *     (VC_SOLVED, VC_MAX_ITER, VC_NONFINITE, VC_OUT_OF_DOMAIN, and VC_INFEASIBLE where
+ *     vc_set_infeasibility turned the detection on); no exception-style failure, unlike the
  *     reference simulator's catch-all (simulation/racing.py:416-423).
  *   - Threading: one context per device per host thread; calls on one context
  *     are serialised on its stream.
@@ -76,7 +77,11 @@ enum vc_tyre { VC_TYRE_FIALA = 0, VC_TYRE_LINEAR = 1 };
  * model's domain (Ux > 0 and s' = (Ux cos epsi - Uy sin epsi) / (1 - kappa ey) > 0 at every
  * stage, dynamic_car.py:169-191 divides by s') although every QP converged: the SQP started
  * from a warm start outside the domain and never got back in.  Not a solution of the NLP. */
-enum vc_status { VC_SOLVED = 0, VC_MAX_ITER = 1, VC_NONFINITE = 2, VC_OUT_OF_DOMAIN = 3 };
+/* VC_INFEASIBLE (ABI 13, additive; kinematic stagewise kernel with vc_set_infeasibility on): the
+ * QP's linearised rows C dz <= d have no feasible point, proved inside the interior point by a
+ * Farkas vector (vc_get_farkas).  u* / x* / u0 are the warm start and its prediction (dz = 0).
+ * Never reported unless the detection is on: such a QP then ends VC_MAX_ITER as before. */
+enum vc_status { VC_SOLVED = 0, VC_MAX_ITER = 1, VC_NONFINITE = 2, VC_OUT_OF_DOMAIN = 3, VC_INFEASIBLE = 4 };
 enum vc_error {
   VC_OK = 0,
   VC_E_ARG = -1,      /* bad argument / dimension */
@@ -130,7 +135,9 @@ typedef struct vc_qp {
   int32_t polish;   /* active-set polish rounds after the interior point (0 = off) */
   int32_t solver;   /* solve-kernel choice (ABI 5).  Kinematic: 0 = condensed (kin_ltv.hip) where
                        built (N = 20) and kin_sqp == 0, else stagewise Riccati (kin_ric.hip);
-                       1 = stagewise Riccati always.  Cascaded: 0 / 1 = stagewise Riccati (casc_ric.hip),
+                       1 = stagewise Riccati always; with vc_set_infeasibility on, 0 routes N = 20 to the
+                       stagewise kernel too (the detection lives there), as elastic > 0 does.
+                       Cascaded: 0 / 1 = stagewise Riccati (casc_ric.hip),
                        2 = condensed (casc_sqp.hip, M = 40 only).  Single-track: the dtype
                        picks the kernel (VC_F32: dyn_sqp.hip, VC_F64: st_sqp.hip). */
   int32_t kin_sqp;  /* kinematic (ABI 6): 0 = one LTV-QP step (the C2 contract); k > 0 = k SQP
@@ -228,6 +235,30 @@ int vc_set_stream(vc_ctx* ctx, void* stream);
 int vc_set_obstacles(vc_ctx* ctx, int n, const double* s, const double* ey, const double* radius,
                      double margin_min);
 int vc_synchronize(vc_ctx* ctx);
+
+/* Infeasibility detection (ABI 13, additive).  on != 0: a kinematic QP with hard rows whose
+ * linearised rows C dz <= d (oracle/ltv_qp.py kin_qp: 4N input-box / trust-region rows, then
+ * 3(N-1) state rows) have no feasible point ends with status VC_INFEASIBLE as soon as the
+ * interior point's multipliers prove it, instead of running to max_iter: with y = lam / |lam|_1
+ * (y >= 0, sum y = 1) and R = sum over the stages of max(d_up, d_dn) for a and for w (every
+ * feasible dz has |dz|_1 <= R),
+ *     d'y + R |C'y|_inf < -eps   =>   no dz satisfies C dz <= d
+ * (y'C dz <= y'd and y'C dz >= -|C'y|_inf R cannot both hold).  eps <= 0 keeps the default 1e-9,
+ * a roundoff guard.  QPs with elastic rows (vc_qp.elastic > 0, or the second pass of elastic < 0)
+ * always have a solution and are not tested.  On VC_INFEASIBLE iters is the count so far, the
+ * outputs are the warm start and its prediction, and vc_solve_diag's diag[2] has bit 32 set.
+ * Default off: the context then behaves exactly as before.  Turning it on routes an N = 20,
+ * vc_qp.solver = 0 context to the stagewise kernel (see vc_qp.solver).  VC_E_UNSUPPORTED on
+ * dynamic / cascaded contexts and on kinematic horizons the stagewise kernel is not built for. */
+int vc_set_infeasibility(vc_ctx* ctx, int on, double eps);
+
+/* The Farkas vectors y[B][7N-3] (fp64) of the last vc_solve* on this context, rows in the order
+ * of oracle/ltv_qp.py kin_qp: [a <=, -a <=, w <=, -w <=] for k = 0..N-1, then [-v, +delta, -delta]
+ * for k = 1..N-1.  Rows of problems that did not end VC_INFEASIBLE are zero.  y follows the
+ * pointer convention of `flags` (ABI 13, additive).  VC_E_ARG when the detection is off or B
+ * exceeds the last solve's batch; VC_E_UNSUPPORTED on vc_qp.kin_sqp > 0 contexts, where several
+ * QPs ran. */
+int vc_get_farkas(vc_ctx* ctx, int B, void* y, int flags);
 
 /* One MPC step for B problems (B <= max_batch):
  *   in:     x0[B][nx], kappa[B][N], ds[B][N], ubar[B][N][nu] (warm start)

@@ -26,6 +26,11 @@
 //              point itself loses accuracy once barrier weights reach ~1e10 (cancellation
 //              in P = Hxx - Hxu Huu^-1 Hux), so the exact answer comes from the polish.
 //   output     u* = ubar + du, x* = xbar + dx (t from the t-rows), u0, status, iterations.
+//   infeasible (DET instantiation, vc_set_infeasibility): from the second iteration, with hard rows,
+//              y = lam / |lam|_1 is tested as a Farkas vector of the rows C dz <= d: the input boxes bound
+//              |dz|_1 <= R, so d'y + R |C'y|_inf < 0 proves that no dz exists.  C'y, condensed
+//              through the dynamics, is the adjoint sweep of the dual residual run on the rows' part of the
+//              stage gradients alone.  The problem then ends VC_INFEASIBLE with dz = 0 and y in A.farkas.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -122,7 +127,7 @@ __device__ __forceinline__ void qmul(const double* Q, const double* v, double* o
   o[5] += Q[O45] * v[4];
 }
 
-template <int N>
+template <int N, bool DET>
 __global__ __launch_bounds__(WTH) void kin_ric_kernel(KinLtvArgs A) {
   static_assert(N >= 2 && N + 1 <= WTH, "one lane per stage");
   __shared__ KrSmem<N> s;
@@ -567,10 +572,10 @@ __global__ __launch_bounds__(WTH) void kin_ric_kernel(KinLtvArgs A) {
   };
 
   // condensed dual residual max |d/du (sum_k gr_k . v_k)| through the dynamics (adjoint sweep)
-  auto dual_residual = [&]() -> double {
-    double rho = l < NXT ? s.gr[N][l] : 0.0, rmax = 0.0;
+  auto adjoint_max = [&](const double (*vec)[NV]) -> double {
+    double rho = l < NXT ? vec[N][l] : 0.0, rmax = 0.0;
     BwdOps A3, B3;
-    bwd_load(N - 1, s.gr, A3);
+    bwd_load(N - 1, vec, A3);
     auto rstage = [&](const BwdOps& o) {
       const double g = bwd_g(o, rho);
       rmax = fu ? fmax(rmax, fabs(g)) : rmax;
@@ -579,15 +584,16 @@ __global__ __launch_bounds__(WTH) void kin_ric_kernel(KinLtvArgs A) {
 #pragma unroll 1
     for (int kk = N - 1; kk >= 0; kk -= 2) {
       const int k1 = kk >= 1 ? kk - 1 : 0, k2 = kk >= 2 ? kk - 2 : 0;
-      bwd_load(k1, s.gr, B3);
+      bwd_load(k1, vec, B3);
       rstage(A3);
       if (kk >= 1) {
-        bwd_load(k2, s.gr, A3);
+        bwd_load(k2, vec, A3);
         rstage(B3);
       }
     }
     return wmax(rmax);
   };
+  auto dual_residual = [&]() -> double { return adjoint_max(s.gr); };
 
   // ---------------- active-set polish ----------------
   // true when certified; the polished stage vectors are then in s.v.  Elastic rows (el) have a
@@ -715,6 +721,11 @@ __global__ __launch_bounds__(WTH) void kin_ric_kernel(KinLtvArgs A) {
   // the adjoint sweep runs at the first iteration and wherever the carried value would end the loop
   double rd_carry = 0.0;
   bool have_rd = false;
+  // infeasibility test (DET): R = sum over the input boxes of max(d_up, d_dn) bounds |dz|_1 of every
+  // feasible dz; off where rows are elastic (those QPs always have a solution)
+  bool infeas = false;
+  double Rbox = 0.0;
+  if constexpr (DET) Rbox = wsum(l < N ? fmax(d[0], d[1]) + fmax(d[2], d[3]) : 0.0);
 #pragma unroll 1
   for (; finite_pred && it < A.qp.max_iter; ++it) {
     // (a) residuals, stage gradients, barrier-augmented stage Hessians
@@ -776,6 +787,35 @@ __global__ __launch_bounds__(WTH) void kin_ric_kernel(KinLtvArgs A) {
       if (!(last_res == last_res) || last_res > 1e300) { fail = true; break; }
     }
     if (last_res <= tol_r && mu <= tol_mu) { conv = true; break; }
+    if constexpr (DET) {
+      if (rho_el == 0.0 && it >= 1) {
+        double dl = 0.0, l1 = 0.0;
+#pragma unroll
+        for (int i = 0; i < NRW; ++i) {
+          dl += m[i] * la[i] * d[i];
+          l1 += m[i] * la[i];
+        }
+        dl = wsum(dl);
+        l1 = wsum(l1);
+        if (dl < 0.0 && l1 > 0.0) {  // uniform; the sweep only where the rows' bound can certify
+          // C'lam through the dynamics: the adjoint sweep on the rows' part of the stage gradients
+          // (s.h is free here: set_h and the polish write it before they read it)
+          if (stl) {
+            double ck[NV];
+#pragma unroll
+            for (int e = 0; e < NV; ++e) ck[e] = 0.0;
+#pragma unroll
+            for (int i = 0; i < NRW; ++i) ck[row_var(i)] += row_sgn(i) * m[i] * la[i];
+#pragma unroll
+            for (int e = 0; e < NV; ++e) s.h[k][e] = ck[e];
+          }
+          WSYNC();
+          const double cmax = adjoint_max(s.h);
+          WSYNC();
+          if ((dl + Rbox * cmax) / l1 < -A.detect_eps) { infeas = true; break; }
+        }
+      }
+    }
     // polish attempts at mu <= 1e-7 and, if that active set does not certify, at 1e-10
     if (A.qp.polish > 0 && mu <= mu_next_polish) {
       tried_polish = true;
@@ -909,6 +949,30 @@ __global__ __launch_bounds__(WTH) void kin_ric_kernel(KinLtvArgs A) {
     WSYNC();
   }
   const bool solved = finite_pred && (polished || conv);
+  if constexpr (DET) {
+    // VC_INFEASIBLE returns the warm start and its prediction (dz = 0); the certificate y = lam / |lam|_1
+    // goes out in the oracle's row order: the input rows of stage 0..N-1, then the state rows of 1..N-1
+    if (infeas && stl) {
+#pragma unroll
+      for (int e = 0; e < NV; ++e) s.v[k][e] = 0.0;
+    }
+    WSYNC();
+    if (A.farkas) {
+      double l1 = 0.0;
+#pragma unroll
+      for (int i = 0; i < NRW; ++i) l1 += m[i] * la[i];
+      l1 = wsum(l1);
+      double* fk = A.farkas + (size_t)b * (7 * N - 3);
+      if (l < N) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) fk[4 * l + i] = infeas ? m[i] * la[i] / l1 : 0.0;
+      }
+      if (l >= 1 && l < N) {
+#pragma unroll
+        for (int i = 4; i < NRW; ++i) fk[4 * N + 3 * (l - 1) + (i - 4)] = infeas ? m[i] * la[i] / l1 : 0.0;
+      }
+    }
+  }
 
   // ---------------- outputs: u* = ubar + du, x* = xbar + dx, u0, status ----------------
   {
@@ -958,6 +1022,7 @@ __global__ __launch_bounds__(WTH) void kin_ric_kernel(KinLtvArgs A) {
     int32_t st;
     if (!finite || !finite_pred) st = VC_NONFINITE;
     else if (solved) st = VC_SOLVED;
+    else if (infeas) st = VC_INFEASIBLE;
     else st = VC_MAX_ITER;
     A.status[b] = st;
     // the elastic-on-failure pass adds its iterations to the hard-row pass's (read before overwriting)
@@ -966,7 +1031,7 @@ __global__ __launch_bounds__(WTH) void kin_ric_kernel(KinLtvArgs A) {
       A.diag[(size_t)b * DS + 0] = last_res;
       A.diag[(size_t)b * DS + 1] = last_mu;
       A.diag[(size_t)b * DS + 2] =
-          double((fail ? 1 : 0) | (conv ? 2 : 0) | (polished ? 4 : 0) | (pol_fact_fail ? 8 : 0));
+          double((fail ? 1 : 0) | (conv ? 2 : 0) | (polished ? 4 : 0) | (pol_fact_fail ? 8 : 0) | (infeas ? 32 : 0));
       A.diag[(size_t)b * DS + 3] = double(rounds_used);
     }
   }
@@ -993,7 +1058,8 @@ hipError_t launch_kin_ric(const KinLtvArgs& a, int N, hipStream_t stream) {
   switch (N) {
 #define VC_CASE(n)                                                                 \
   case n:                                                                          \
-    hipLaunchKernelGGL((kin_ric_kernel<n>), dim3(a.B), dim3(WTH), 0, stream, a);  \
+    if (a.detect) hipLaunchKernelGGL((kin_ric_kernel<n, true>), dim3(a.B), dim3(WTH), 0, stream, a);   \
+    else hipLaunchKernelGGL((kin_ric_kernel<n, false>), dim3(a.B), dim3(WTH), 0, stream, a);           \
     return hipGetLastError();
     VC_KR_HORIZONS(VC_CASE)
 #undef VC_CASE

@@ -195,6 +195,11 @@ struct KinLtvArgs {
   vc_kin_mpc w;
   vc_qp qp;
   vc_obstacles obs;
+  // infeasibility detection (vc_set_infeasibility; kin_ric.hip only, appended so that the offsets
+  // kin_ltv.hip reads stay where they were)
+  int detect;           // 1: the Farkas test runs inside the interior point (status VC_INFEASIBLE)
+  double detect_eps;    // roundoff guard of the test
+  double* farkas;       // [B][7N-3] certificate y in the row order of oracle/ltv_qp.py kin_qp, may be null
 };
 
 // Merit line search of the kinematic SQP step (kin_merit.hip; vc_qp.kin_sqp > 0).

@@ -33,6 +33,11 @@ struct vc_ctx {
   void* jw = nullptr;     // single-track / cascaded SQP: stage Jacobians of the kernels that keep them out of LDS
   size_t jw_bytes = 0;
   int fault_iter = -1, fault_problem = -1;  // vc_debug_qp_fault (tests only)
+  // vc_set_infeasibility: the Farkas test of the stagewise kinematic kernel and its certificates
+  bool detect = false;
+  double detect_eps = 1e-9;
+  void* farkas = nullptr;  // [max_batch][7N-3] fp64, allocated on first enable
+  int farkas_B = 0;        // batch of the last solve that wrote it
   std::string err;
 };
 
@@ -146,11 +151,14 @@ vc::TrackTable track_table(const vc_ctx* c) {
 // the condensed kernel for the one-step contract only: the globalised step's QPs (obstacle
 // barriers, condition numbers ~1e6) need the stagewise factorisation's accuracy (kin_ric.hip
 // matches the oracle to 1e-8 there, the condensed normal equations to 8e-5; scripts/kin_sqp_debug.py)
-bool kin_condensed(const vc_ctx* c) {
+bool kin_condensed_cfg(const vc_ctx* c) {
   // elastic rows (qp.elastic) and multiple shooting are built in the stagewise kernel only
   return vc::kin_ltv_smem_bytes(c->N) > 0 && c->p.qp.solver == 0 && c->p.qp.kin_sqp <= 0 && !c->p.qp.ms &&
          c->p.qp.elastic == 0.0;
 }
+// ... and so is the infeasibility detection (vc_set_infeasibility): the solve of a context that has it
+// on goes to the stagewise kernel; vc_condense keeps the condensed kernel's H, g either way
+bool kin_condensed(const vc_ctx* c) { return kin_condensed_cfg(c) && !c->detect; }
 bool kin_solve_built(const vc_ctx* c) {
   return c->model == VC_MODEL_KINEMATIC && c->dtype == VC_F64 && (kin_condensed(c) || vc::kin_ric_built(c->N));
 }
@@ -449,6 +457,7 @@ void vc_destroy(vc_ctx* c) {
   if (c->sim) (void)hipFree(c->sim);
   if (c->ls) (void)hipFree(c->ls);
   if (c->jw) (void)hipFree(c->jw);
+  if (c->farkas) (void)hipFree(c->farkas);
   if (c->own) (void)hipStreamDestroy(c->own);
   delete c;
 }
@@ -482,6 +491,41 @@ int vc_set_obstacles(vc_ctx* c, int n, const double* s, const double* ey, const 
 int vc_synchronize(vc_ctx* c) {
   if (!c) return VC_E_ARG;
   VC_HIP(c, hipSetDevice(c->device));
+  VC_HIP(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int vc_set_infeasibility(vc_ctx* c, int on, double eps) {
+  if (!c) return VC_E_ARG;
+  if (c->model != VC_MODEL_KINEMATIC || c->dtype != VC_F64 || !vc::kin_ric_built(c->N))
+    return fail(c, VC_E_UNSUPPORTED,
+                "vc_set_infeasibility: the stagewise kinematic kernel only (kinematic fp64, N=10..60 step 10); "
+                "model=%d dtype=%d N=%d", c->model, c->dtype, c->N);
+  if (on && !c->farkas) {
+    VC_HIP(c, hipSetDevice(c->device));
+    const size_t bytes = (size_t)(c->max_batch > 0 ? c->max_batch : 1) * (7 * c->N - 3) * 8;
+    VC_HIP(c, hipMalloc(&c->farkas, bytes));
+  }
+  c->detect = on != 0;
+  c->detect_eps = eps > 0.0 ? eps : 1e-9;
+  c->farkas_B = 0;  // no solve has written certificates under this setting yet
+  return 0;
+}
+
+int vc_get_farkas(vc_ctx* c, int B, void* y, int flags) {
+  if (int r = check_common(c, B, flags)) return r;
+  if (!c->detect || !c->farkas) return fail(c, VC_E_ARG, "vc_get_farkas: infeasibility detection is off");
+  if (c->p.qp.kin_sqp > 0)
+    return fail(c, VC_E_UNSUPPORTED, "vc_get_farkas: kin_sqp > 0 solves several QPs per call");
+  if (B > c->farkas_B) return fail(c, VC_E_ARG, "vc_get_farkas: B=%d exceeds the last solve's %d", B, c->farkas_B);
+  if (!y) return fail(c, VC_E_ARG, "null pointer");
+  if (B == 0) return 0;
+  const size_t bytes = (size_t)B * (7 * c->N - 3) * 8;
+  if (flags == VC_DEVICE_PTRS) {
+    VC_HIP(c, hipMemcpyAsync(y, c->farkas, bytes, hipMemcpyDeviceToDevice, c->stream));
+    return 0;
+  }
+  VC_HIP(c, hipMemcpyAsync(y, c->farkas, bytes, hipMemcpyDeviceToHost, c->stream));
   VC_HIP(c, hipStreamSynchronize(c->stream));
   return 0;
 }
@@ -577,6 +621,12 @@ static int kin_solve(vc_ctx* c, int B, const void* x0, const void* kappa, const 
     a.diag = (double*)diag;
   }
   a.x_in = a.x_out;  // multiple shooting (qp.ms): the warm-start states arrive in xbar
+  if (c->detect) {  // kin_condensed(c) is false then: every launch below is the stagewise kernel's
+    a.detect = 1;
+    a.detect_eps = c->detect_eps;
+    a.farkas = (double*)c->farkas;
+    c->farkas_B = B;
+  }
   const int S = c->p.qp.kin_sqp;
   if (S > 0 && (const void*)a.ubar != (const void*)a.u_out) {
     // the SQP iterates in place: start it on u_out
@@ -691,7 +741,7 @@ int vc_condense(vc_ctx* c, int B, const void* x0, const void* ubar, const void* 
   if (int r = check_common(c, B, flags)) return r;
   const bool casc_cond = c->model == VC_MODEL_CASCADED && c->dtype == VC_F64 &&
                          vc::casc_sqp_built(c->N, c->p.casc.horizon_pm);
-  if (!(kin_solve_built(c) && kin_condensed(c)) && !casc_cond)
+  if (!(kin_solve_built(c) && kin_condensed_cfg(c)) && !casc_cond)
     return fail(c, VC_E_UNSUPPORTED, "vc_condense: model=%d dtype=%d N=%d not built", c->model, c->dtype, c->N);
   if (!x0 || !kappa || !ds || !ubar || !H || !g) return fail(c, VC_E_ARG, "null pointer");
   if (B == 0) return 0;

@@ -20,11 +20,11 @@ VC_MODEL_KINEMATIC, VC_MODEL_DYNAMIC, VC_MODEL_CASCADED = 0, 1, 2
 VC_F64, VC_F32 = 0, 1
 VC_HOST_PTRS, VC_DEVICE_PTRS = 0, 1
 VC_TYRE_FIALA, VC_TYRE_LINEAR = 0, 1
-VC_SOLVED, VC_MAX_ITER, VC_NONFINITE, VC_OUT_OF_DOMAIN = 0, 1, 2, 3
+VC_SOLVED, VC_MAX_ITER, VC_NONFINITE, VC_OUT_OF_DOMAIN, VC_INFEASIBLE = 0, 1, 2, 3, 4
 VC_OK, VC_E_ARG, VC_E_HIP, VC_E_UNSUPPORTED = 0, -1, -2, -3
 
 STATUS_NAMES = {VC_SOLVED: "solved", VC_MAX_ITER: "max_iter", VC_NONFINITE: "nonfinite",
-                VC_OUT_OF_DOMAIN: "out_of_domain"}
+                VC_OUT_OF_DOMAIN: "out_of_domain", VC_INFEASIBLE: "infeasible"}
 
 
 class vc_kin_car(C.Structure):
@@ -95,6 +95,8 @@ PROTOTYPES = {
     "vc_set_stream": (C.c_int, [_vp, _vp]),
     "vc_synchronize": (C.c_int, [_vp]),
     "vc_set_obstacles": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_double]),
+    "vc_set_infeasibility": (C.c_int, [_vp, C.c_int, C.c_double]),
+    "vc_get_farkas": (C.c_int, [_vp, C.c_int, _vp, C.c_int]),
     "vc_solve": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int]),
     "vc_solve_diag": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int]),
     "vc_solve_from": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int]),

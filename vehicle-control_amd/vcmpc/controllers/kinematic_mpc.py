@@ -116,9 +116,14 @@ class BatchedKinematicMPC(Controller):
         cfg["qp"] = kin_qp_block(config)
         self.shift = bool(cfg["qp"].get("shift", 0))
         self.ms = bool(cfg["qp"].get("ms", 0))
+        # qp.detect_infeasible (default false): a first solve whose linearised rows have no feasible
+        # point comes back VC_INFEASIBLE, Farkas-certified, instead of running to max_iter
+        # (vc_set_infeasibility); the neutral retry below handles it like any other status != 0
+        self.detect_infeasible = bool(cfg["qp"].get("detect_infeasible", False))
         self.ctx = Context(model=_abi.VC_MODEL_KINEMATIC, N=self.N, max_batch=self.B, dtype=_abi.VC_F64,
                            device=device, params=make_params(kin_car=car.config, kin_mpc=cfg,
-                                                             obstacles=obstacle_list(car, config)))
+                                                             obstacles=obstacle_list(car, config)),
+                           detect_infeasible=self.detect_infeasible)
         # warm starts: kinematic_mpc.py:64-68 (zeros, v = 0.1; actions 1 + U[0,1) seeded)
         rng = np.random.RandomState(seed) if seed is not None else np.random
         self.state_prediction = np.zeros((self.B, self.ns, self.N + 1))
@@ -126,6 +131,8 @@ class BatchedKinematicMPC(Controller):
         self.action_prediction = np.ones((self.B, self.na, self.N)) + rng.random_sample((self.B, self.na, self.N))
         self.status = np.zeros(self.B, np.int32)
         self.iters = np.zeros(self.B, np.int32)
+        # per vehicle: control steps whose first solve was certified infeasible (qp.detect_infeasible)
+        self.infeasible_steps = np.zeros(self.B, np.int64)
 
     def command(self, states):
         """states[B, ns] -> actions[B, na] (u*_0 of every problem).
@@ -152,6 +159,7 @@ class BatchedKinematicMPC(Controller):
         xs = np.ascontiguousarray(np.swapaxes(self.state_prediction, 1, 2)) if self.ms else None
         u0, xbar, ustar, status, iters = self.ctx.solve(x0, kappa, ds, ubar, xbar=xs)
         bad = status != 0
+        self.infeasible_steps += status == _abi.VC_INFEASIBLE
         if bad.any():
             # retry from the neutral warm start u = 0 (steering held, speed held):
             # its linearised state rows are feasible at dz = 0 whenever x0 is

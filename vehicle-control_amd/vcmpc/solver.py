@@ -35,7 +35,8 @@ class Context:
     """One solve context (one device, one model, one horizon, one stream)."""
 
     def __init__(self, model: int = _abi.VC_MODEL_KINEMATIC, N: int = 20, max_batch: int = 1024,
-                 dtype: int = _abi.VC_F64, device: int = 0, params: _abi.vc_params | None = None, **cfgs):
+                 dtype: int = _abi.VC_F64, device: int = 0, params: _abi.vc_params | None = None,
+                 detect_infeasible: bool = False, infeasible_eps: float = 0.0, **cfgs):
         self.lib = _abi.load_library()
         self.model, self.N, self.max_batch, self.dtype, self.device = model, int(N), int(max_batch), dtype, device
         self.nx = NX[model]
@@ -48,6 +49,14 @@ class Context:
         if not h:
             raise _abi.VcError(_abi.VC_E_HIP, self.lib.vc_last_error(None).decode())
         self._h = C.c_void_p(h)
+        self.detect_infeasible = False
+        self._last = None  # (B, device or None) of the last solve: what farkas() returns
+        if detect_infeasible:
+            try:
+                self.set_infeasibility(True, infeasible_eps)
+            except Exception:
+                self.close()
+                raise
 
     # -- lifetime ---------------------------------------------------------------
     def close(self):
@@ -81,6 +90,34 @@ class Context:
         cols = [np.ascontiguousarray(rows[:, i]) for i in range(3)]
         self._check(self.lib.vc_set_obstacles(self._h, len(rows), *[C.c_void_p(c.ctypes.data) for c in cols],
                                               float(margin_min)))
+
+    def set_infeasibility(self, on: bool, eps: float = 0.0):
+        """``vc_set_infeasibility``: in-kernel infeasibility detection of the stagewise kinematic
+        kernel.  On: a QP whose linearised rows have no feasible point ends with status
+        ``VC_INFEASIBLE`` (4), proved by the Farkas vector ``farkas()`` returns; ``eps <= 0`` keeps
+        the default roundoff guard 1e-9.  Raises ``VcError`` (VC_E_UNSUPPORTED) on dynamic /
+        cascaded contexts."""
+        self._check(self.lib.vc_set_infeasibility(self._h, int(bool(on)), float(eps)))
+        self.detect_infeasible = bool(on)
+        self._last = None
+
+    def farkas(self, B: int | None = None):
+        """``vc_get_farkas``: y[B, 7N - 3] of the last solve (rows in the order of
+        oracle/ltv_qp.py ``kin_qp``; zero for problems that did not end ``VC_INFEASIBLE``), a
+        numpy array after a host-array solve, a torch tensor on the context's device after a
+        device-tensor one.  Raises ``VcError`` when the detection is off."""
+        last_B, dev = self._last if self._last is not None else (0, None)
+        B = last_B if B is None else int(B)
+        m = 7 * self.N - 3
+        if dev is not None:
+            import torch
+            y = torch.empty((B, m), dtype=torch.float64, device=dev)
+            ptr, flags = C.c_void_p(y.data_ptr()), _abi.VC_DEVICE_PTRS
+        else:
+            y = np.empty((B, m), np.float64)
+            ptr, flags = C.c_void_p(y.ctypes.data), _abi.VC_HOST_PTRS
+        self._check(self.lib.vc_get_farkas(self._h, B, ptr, flags))
+        return y
 
     def synchronize(self):
         self._check(self.lib.vc_synchronize(self._h))
@@ -141,6 +178,7 @@ class Context:
         bufs = [x0, kappa, ds, xbar, ubar, u0, status, iters]
         shapes = [(B, nx), (B, N), (B, N), (B, NS, nx), (B, N, NU), (B, NU), (B,), (B,)]
         dts = [f, f, f, f, f, f, np.int32, np.int32]
+        self._last = (B, x0.device if _is_torch(x0) else None)
         if diag is not None and diag is not False:
             if diag is True:
                 diag = self._like(x0, (B, 4))
@@ -172,6 +210,7 @@ class Context:
             status = np.empty((B,), np.int32) if status is None else status
             iters = np.empty((B,), np.int32) if iters is None else iters
         bufs = [x0, kappa, ds, ubar_in, xbar, u_out, u0, status, iters]
+        self._last = (B, x0.device if _is_torch(x0) else None)
         shapes = [(B, nx), (B, N), (B, N), (B, N, NU), (B, NS, nx), (B, N, NU), (B, NU), (B,), (B,)]
         dts = [f, f, f, f, f, f, f, np.int32, np.int32]
         ptrs, flags = self._marshal(bufs, shapes, dts)
