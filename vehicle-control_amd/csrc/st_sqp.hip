@@ -22,6 +22,11 @@
 //              Lane k owns stage k's rows, slacks and multipliers in registers; the
 //              recursions run on lanes 0..44 with the stage matrices in LDS.
 //   update     ubar += dz (Fx scaled back by fx_scale)
+//   infeasible (DET instantiation, vc_set_sqp_infeasibility): from the second interior-point iteration of
+//              every QP, y = lam / |lam|_1 is tested as a Farkas vector of the rows C dz <= d: the Fx trust
+//              region and the w box bound |dz|_1 <= R, so d'y + R |C'y|_inf < 0 proves that no dz exists
+//              (DESIGN.md 11).  The first QP: the problem ends VC_INFEASIBLE at its warm start; a later
+//              one: the existing `stopped` path, only sooner.  y goes to A.farkas, the QP to A.qp_index.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -288,7 +293,7 @@ __device__ __forceinline__ StJP<N, JG> st_jac(StSmem<N, JG>& s, const StSqpArgs&
   else return s.J;
 }
 
-template <int N, int TYRE, bool JG>
+template <int N, int TYRE, bool JG, bool DET>
 __global__ __launch_bounds__(WTH) void st_sqp_kernel(StSqpArgs A) {
   static_assert(N >= 2 && N <= WTH, "one lane per stage");
   // occupancy guard (rocprofv3 LDS_Block_Size: 53,248 B ran three one-wave workgroups per CU,
@@ -340,6 +345,7 @@ __global__ __launch_bounds__(WTH) void st_sqp_kernel(StSqpArgs A) {
   int it_total = 0, it_max = 0;
   bool all_conv = true, any_fail = false, stopped = false;  // stopped: a later QP ended the SQP early
   bool all_pol = true;  // every converged QP's answer certified by the active-set polish
+  bool cert = false;    // DET: a QP was certified infeasible (its Farkas vector is in A.farkas)
   double last_res = 0.0, last_mu = 0.0;
   const double tol_r = 1e-10, tol_mu = 1e-13;
 
@@ -976,9 +982,75 @@ __global__ __launch_bounds__(WTH) void st_sqp_kernel(StSqpArgs A) {
       for (int e = 0; e < NQ; ++e) s.u.q.Qt[k][e] = Qt[e];
     };
 
+    // Infeasibility test (DET): y = lam / |lam|_1 is a Farkas vector of the rows
+    // C dz <= d when d'y + R |C'y|_inf < 0, R = sum_k [trust_Fx / S + max(0, up_k, dn_k)] >= |dz|_1 of
+    // every feasible dz (rows 8..11 are boxes).  C'y on the inputs is the open-loop adjoint sweep of
+    // the rows' stage vectors sum_i m_i lam_i c_i; it runs only when d'lam < 0.  It borrows s.u.q.g and
+    // puts the stage gradients grk back (a carried dual residual may still be replaced by a sweep of
+    // them; set_h rewrites g from registers afterwards).  The guard is relative to
+    // the magnitude of the terms the value is summed from, the sweep's costates included: at low
+    // speed the open-loop sweep amplifies rounding (see dual_residual) and the value is then
+    // accurate to that magnitude only.
+    [[maybe_unused]] auto farkas_test = [&](const double* grk) -> bool {
+      double dl = 0.0, l1 = 0.0;
+#pragma unroll
+      for (int i = 0; i < NR; ++i) {
+        dl += R.m[i] * la[i] * R.d[i];
+        l1 += R.m[i] * la[i];
+      }
+      dl = wsum(dl);
+      l1 = wsum(l1);
+      if (!(dl < 0.0) || !(l1 > 0.0) || !(l1 < 1e300)) return false;  // uniform
+      double dab = 0.0;
+      if (stl) {
+        double ml[NR], ck[9];
+#pragma unroll
+        for (int i = 0; i < NR; ++i) {
+          ml[i] = R.m[i] * la[i];
+          dab += ml[i] * fabs(R.d[i]);
+        }
+#pragma unroll
+        for (int e = 0; e < 9; ++e) ck[e] = 0.0;
+        row_adjoint(R, ml, ck);
+#pragma unroll
+        for (int e = 0; e < 9; ++e) s.u.q.g[k][e] = ck[e];
+      }
+      WSYNC();
+      BwdOps A4, B4;
+      bwd_load(N - 1, s.u.q.g, A4);
+      double rho = 0.0, cmax = 0.0, amax = 0.0;
+      auto cstage = [&](int kk, const BwdOps& o) {
+        rho = bwd_g(kk, o, rho);
+        cmax = fk ? fmax(cmax, fabs(rho)) : cmax;
+        amax = fmax(amax, fabs(rho));
+      };
+#pragma unroll 1
+      for (int kk = N - 1; kk >= 0; kk -= 2) {
+        const int k1 = kk >= 1 ? kk - 1 : 0, k2 = kk >= 2 ? kk - 2 : 0;
+        bwd_load(k1, s.u.q.g, B4);
+        cstage(kk, A4);
+        if (kk >= 1) {
+          bwd_load(k2, s.u.q.g, A4);
+          cstage(kk - 1, B4);
+        }
+      }
+      if (stl) {
+#pragma unroll
+        for (int e = 0; e < 9; ++e) s.u.q.g[k][e] = grk[e];
+      }
+      WSYNC();
+      cmax = wmax(cmax);
+      amax = wmax(amax);
+      dab = wsum(dab);
+      const double rb = wsum(stl ? (R.m[10] > 0.0 ? R.d[10] : 1e300) + fmax(0.0, fmax(R.d[8], R.d[9])) : 0.0);
+      // (d'y + R |C'y|_inf < -eps (1 + magnitude), times |lam|_1; a NaN anywhere compares false)
+      return dl + rb * cmax < -A.detect_eps * (l1 + dab + rb * amax);
+    };
+
     // ---------------- interior point (Mehrotra predictor-corrector) ----------------
     int it = 0;
     bool conv = false, fail = false;
+    bool infeas = false;  // DET: this QP's rows are certified infeasible
     // dual residual carried by the steps: the LQ direction solves the linearised
     // stationarity exactly, so a step of length alpha scales the condensed gradient by
     // (1 - alpha); the adjoint sweep runs at the first iteration and wherever the carried value
@@ -1028,6 +1100,11 @@ __global__ __launch_bounds__(WTH) void st_sqp_kernel(StSqpArgs A) {
       ST_ACC(ST_DUAL, t_d0)
       last_res = fmax(rdm, rpm);
       last_mu = mu;
+      if constexpr (DET) {
+        // ahead of the three exits through `fail` below (non-finite residuals, factorisation
+        // breakdown: none of them changes the multipliers), so a diverging QP is still labelled
+        if (it >= 1 && farkas_test(grk)) { infeas = true; break; }
+      }
       if (!(last_res == last_res) || !(mu == mu) || last_res > 1e300) { fail = true; break; }
       if (have_rd && mu <= 1e2 * tol_mu && fmax(rdm, rpm) <= 1e3 * rtol) {
         // the carried value would end the loop here or below: take the sweep's
@@ -1133,6 +1210,28 @@ __global__ __launch_bounds__(WTH) void st_sqp_kernel(StSqpArgs A) {
     }
     it_total += it;
     it_max = max(it_max, it);
+    if constexpr (DET) {
+      // the certificate y = lam / |lam|_1 goes out in the oracle's row order
+      if (infeas) {
+        double l1 = 0.0;
+#pragma unroll
+        for (int i = 0; i < NR; ++i) l1 += R.m[i] * la[i];
+        l1 = wsum(l1);
+        if (stl) {
+          double* fkv = A.farkas + (size_t)b * (12 * N - 3) + (k >= 1 ? 12 * k - 3 : 0);
+#pragma unroll
+          for (int i = 0; i < NR; ++i) {
+            if (i >= 3) fkv[k >= 1 ? i : i - 3] = R.m[i] * la[i] / l1;
+            else if (k >= 1) fkv[i] = R.m[i] * la[i] / l1;
+          }
+        }
+        if (l == 0) A.qp_index[b] = sq;
+        cert = true;
+        // the first QP: the problem ends here, at the warm start and its rollout (s.ub, s.xs);
+        // a later one takes the stopped path below
+        if (sq == 0) break;
+      }
+    }
 
     // ---------------- active-set polish (round 5) ----------------
     // The interior point stops at mu <= 1e-13 with a floor acceptance near the end, and its
@@ -1296,10 +1395,17 @@ __global__ __launch_bounds__(WTH) void st_sqp_kernel(StSqpArgs A) {
     A.x_out[(size_t)b * 8 * N + e] = v;
   }
   finite = __all(finite ? 1 : 0) != 0;
+  if constexpr (DET) {
+    if (!cert) {  // uniform: no certificate, a zero row and -1
+      for (int e = l; e < 12 * N - 3; e += WTH) A.farkas[(size_t)b * (12 * N - 3) + e] = 0.0;
+      if (l == 0) A.qp_index[b] = -1;
+    }
+  }
   if (l < 2) A.u0[(size_t)b * 2 + l] = s.ub[0][l];
   if (l == 0) {
     int32_t st;
     if (!finite || s.flag[0] == VC_NONFINITE) st = VC_NONFINITE;
+    else if (DET && cert && !stopped) st = VC_INFEASIBLE;  // the first QP has no feasible point
     else if (s.flag[2] == 0) st = VC_OUT_OF_DOMAIN;  // x* (the last rollout) outside the model's domain
     else if (all_conv) st = VC_SOLVED;
     else st = VC_MAX_ITER;
@@ -1316,7 +1422,8 @@ __global__ __launch_bounds__(WTH) void st_sqp_kernel(StSqpArgs A) {
       A.diag[(size_t)b * DS + 0] = last_res;
       A.diag[(size_t)b * DS + 1] = last_mu;
       A.diag[(size_t)b * DS + 2] =
-          double((any_fail ? 1 : 0) | (all_conv ? 2 : 0) | (all_pol ? 4 : 0) | (stopped ? 16 : 0));
+          double((any_fail ? 1 : 0) | (all_conv ? 2 : 0) | (all_pol ? 4 : 0) | (stopped ? 16 : 0) |
+                 (DET && cert ? 32 : 0));
       A.diag[(size_t)b * DS + 3] = double(it_max);
     }
   }
@@ -1365,16 +1472,19 @@ template <int N, int TYRE>
 void st_launch(const StSqpArgs& a, hipStream_t stream) {
   if constexpr (st_j_global_ok<N>()) {
     if (st_jg_pick<N>(a.B)) {
-      hipLaunchKernelGGL((st_sqp_kernel<N, TYRE, true>), dim3(a.B), dim3(WTH), 0, stream, a);
+      if (a.detect) hipLaunchKernelGGL((st_sqp_kernel<N, TYRE, true, true>), dim3(a.B), dim3(WTH), 0, stream, a);
+      else hipLaunchKernelGGL((st_sqp_kernel<N, TYRE, true, false>), dim3(a.B), dim3(WTH), 0, stream, a);
       return;
     }
   }
-  hipLaunchKernelGGL((st_sqp_kernel<N, TYRE, false>), dim3(a.B), dim3(WTH), 0, stream, a);
+  if (a.detect) hipLaunchKernelGGL((st_sqp_kernel<N, TYRE, false, true>), dim3(a.B), dim3(WTH), 0, stream, a);
+  else hipLaunchKernelGGL((st_sqp_kernel<N, TYRE, false, false>), dim3(a.B), dim3(WTH), 0, stream, a);
 }
 
 hipError_t launch_st_sqp(const StSqpArgs& a, int N, hipStream_t stream) {
   if (a.B <= 0) return hipSuccess;
   if (st_sqp_jws_doubles(N, a.B) && !a.jws) return hipErrorInvalidValue;  // the workspace the kernel needs
+  if (a.detect && (!a.farkas || !a.qp_index)) return hipErrorInvalidValue;
   const bool lin = a.car.tyre == VC_TYRE_LINEAR;
   switch (N) {
 #define VC_CASE(n)                                        \

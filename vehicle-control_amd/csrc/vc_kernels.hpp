@@ -267,6 +267,12 @@ struct StSqpArgs {
   vc_dyn_mpc w;
   vc_qp qp;
   vc_obstacles obs;
+  // infeasibility detection (vc_set_sqp_infeasibility), appended so that the offsets the kernel
+  // reads without it stay where they were
+  int detect;           // 1: launch the DET instantiation (the Farkas test runs inside each interior point)
+  double detect_eps;    // roundoff guard of the test
+  double* farkas;       // [B][12N-3] certificate y in the row order of oracle/dyn_sqp.py dyn_qp
+  int32_t* qp_index;    // [B] SQP iteration whose QP was certified, -1: none
 };
 
 // Fused cascaded (single-track + point-mass) SQP step (casc_sqp.hip), fp64.

@@ -38,6 +38,12 @@ struct vc_ctx {
   double detect_eps = 1e-9;
   void* farkas = nullptr;  // [max_batch][7N-3] fp64, allocated on first enable
   int farkas_B = 0;        // batch of the last solve that wrote it
+  // vc_set_sqp_infeasibility: the same for the single-track SQP (st_sqp.hip)
+  bool sqp_detect = false;
+  double sqp_detect_eps = 1e-9;
+  void* sqp_farkas = nullptr;    // [max_batch][12N-3] fp64, allocated on first enable
+  void* sqp_qp_index = nullptr;  // [max_batch] int32
+  int sqp_farkas_B = 0;
   std::string err;
 };
 
@@ -308,6 +314,13 @@ int st_solve(vc_ctx* c, int B, const void* x0, const void* kappa, const void* ds
     if (int r = ensure_scratch(c, &c->jw, &c->jw_bytes, (size_t)B * jd * 8)) return r;
     a.jws = (double*)c->jw;
   }
+  if (c->sqp_detect) {
+    a.detect = 1;
+    a.detect_eps = c->sqp_detect_eps;
+    a.farkas = (double*)c->sqp_farkas;
+    a.qp_index = (int32_t*)c->sqp_qp_index;
+    c->sqp_farkas_B = B;
+  }
   VC_HIP(c, vc::launch_st_sqp(a, N, c->stream));
   if (flags == VC_HOST_PTRS) return unstage(c, slots);
   return 0;
@@ -458,6 +471,8 @@ void vc_destroy(vc_ctx* c) {
   if (c->ls) (void)hipFree(c->ls);
   if (c->jw) (void)hipFree(c->jw);
   if (c->farkas) (void)hipFree(c->farkas);
+  if (c->sqp_farkas) (void)hipFree(c->sqp_farkas);
+  if (c->sqp_qp_index) (void)hipFree(c->sqp_qp_index);
   if (c->own) (void)hipStreamDestroy(c->own);
   delete c;
 }
@@ -527,6 +542,41 @@ int vc_get_farkas(vc_ctx* c, int B, void* y, int flags) {
   }
   VC_HIP(c, hipMemcpyAsync(y, c->farkas, bytes, hipMemcpyDeviceToHost, c->stream));
   VC_HIP(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int vc_set_sqp_infeasibility(vc_ctx* c, int on, double eps) {
+  if (!c) return VC_E_ARG;
+  if (c->model != VC_MODEL_DYNAMIC || c->dtype != VC_F64 || !vc::st_sqp_built(c->N))
+    return fail(c, VC_E_UNSUPPORTED,
+                "vc_set_sqp_infeasibility: the single-track fp64 SQP kernel only (dynamic fp64, N=20..60 step 10); "
+                "model=%d dtype=%d N=%d", c->model, c->dtype, c->N);
+  if (!(c->p.dyn_mpc.trust_Fx > 0))
+    return fail(c, VC_E_ARG, "vc_set_sqp_infeasibility: dyn_mpc.trust_Fx must be > 0 (it bounds |dz|_1)");
+  if (on && !c->sqp_farkas) {
+    VC_HIP(c, hipSetDevice(c->device));
+    const size_t nb = (size_t)(c->max_batch > 0 ? c->max_batch : 1);
+    VC_HIP(c, hipMalloc(&c->sqp_farkas, nb * (12 * c->N - 3) * 8));
+    VC_HIP(c, hipMalloc(&c->sqp_qp_index, nb * 4));
+  }
+  c->sqp_detect = on != 0;
+  c->sqp_detect_eps = eps > 0.0 ? eps : 1e-9;
+  c->sqp_farkas_B = 0;  // no solve has written certificates under this setting yet
+  return 0;
+}
+
+int vc_get_sqp_farkas(vc_ctx* c, int B, void* y, int32_t* qp_index, int flags) {
+  if (int r = check_common(c, B, flags)) return r;
+  if (!c->sqp_detect || !c->sqp_farkas || !c->sqp_qp_index)
+    return fail(c, VC_E_ARG, "vc_get_sqp_farkas: infeasibility detection is off");
+  if (B > c->sqp_farkas_B)
+    return fail(c, VC_E_ARG, "vc_get_sqp_farkas: B=%d exceeds the last solve's %d", B, c->sqp_farkas_B);
+  if (!y) return fail(c, VC_E_ARG, "null pointer");
+  if (B == 0) return 0;
+  const hipMemcpyKind kind = flags == VC_DEVICE_PTRS ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  VC_HIP(c, hipMemcpyAsync(y, c->sqp_farkas, (size_t)B * (12 * c->N - 3) * 8, kind, c->stream));
+  if (qp_index) VC_HIP(c, hipMemcpyAsync(qp_index, c->sqp_qp_index, (size_t)B * 4, kind, c->stream));
+  if (flags != VC_DEVICE_PTRS) VC_HIP(c, hipStreamSynchronize(c->stream));
   return 0;
 }
 

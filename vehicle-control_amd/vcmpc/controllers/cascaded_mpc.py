@@ -98,11 +98,16 @@ class BatchedSingleTrackMPC(Controller):
         self.B = int(batch)
         self.np_dtype = np.float64 if dtype == "f64" else np.float32
         vdt = _abi.VC_F64 if dtype == "f64" else _abi.VC_F32
+        # qp.detect_infeasible (default false; fp64): a solve whose first QP has no feasible point comes
+        # back VC_INFEASIBLE, Farkas-certified, instead of applying a diverged iterate
+        # (vc_set_sqp_infeasibility); the neutral retry below handles it like any other status != 0
+        self.detect_infeasible = bool((config.get("qp") or {}).get("detect_infeasible", False))
         self.ctx = Context(model=_abi.VC_MODEL_DYNAMIC, N=self.N, max_batch=self.B, dtype=vdt, device=device,
                            params=make_params(dyn_car=car.config, dyn_mpc=dict(config, qp=dyn_qp_block(config)),
                                               tyre=getattr(car, "tyre", "fiala"),
                                               obstacles=obstacle_list(car, config),
-                                              obstacle_inside=bool(config.get("obstacle_inside", False))))
+                                              obstacle_inside=bool(config.get("obstacle_inside", False))),
+                           detect_infeasible=self.detect_infeasible)
         # warm starts: cascaded_mpc.py:72-76
         rng = np.random.RandomState(seed) if seed is not None else np.random
         self.state_prediction = np.ones((self.B, self.ns, self.N))
@@ -110,6 +115,8 @@ class BatchedSingleTrackMPC(Controller):
         self.action_prediction = np.ones((self.B, self.na, self.N)) + rng.random_sample((self.B, self.na, self.N))
         self.status = np.zeros(self.B, np.int32)
         self.iters = np.zeros(self.B, np.int32)
+        # per vehicle: control steps whose first solve was certified infeasible (qp.detect_infeasible)
+        self.infeasible_steps = np.zeros(self.B, np.int64)
 
     def command(self, states):
         """states[B, ns] -> actions[B, na] (u*_0 of every problem).
@@ -130,6 +137,7 @@ class BatchedSingleTrackMPC(Controller):
         x0f, kf, dsf = cast(x0), cast(kappa), cast(ds)
         u0, xbar, ustar, status, iters = self.ctx.solve(x0f, kf, dsf, ubar)
         bad = status != 0
+        self.infeasible_steps += status == _abi.VC_INFEASIBLE
         if bad.any():
             # the retry is neutral in its horizon too: ds, kappa from the state prediction x0 at
             # every stage (vc_simulate's restart), not from the previous plan the failed solve used

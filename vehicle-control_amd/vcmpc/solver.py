@@ -53,7 +53,11 @@ class Context:
         self._last = None  # (B, device or None) of the last solve: what farkas() returns
         if detect_infeasible:
             try:
-                self.set_infeasibility(True, infeasible_eps)
+                # the single-track fp64 SQP has its own entry point (vc_set_sqp_infeasibility)
+                if model == _abi.VC_MODEL_DYNAMIC and dtype == _abi.VC_F64:
+                    self.set_sqp_infeasibility(True, infeasible_eps)
+                else:
+                    self.set_infeasibility(True, infeasible_eps)
             except Exception:
                 self.close()
                 raise
@@ -118,6 +122,38 @@ class Context:
             ptr, flags = C.c_void_p(y.ctypes.data), _abi.VC_HOST_PTRS
         self._check(self.lib.vc_get_farkas(self._h, B, ptr, flags))
         return y
+
+    def set_sqp_infeasibility(self, on: bool, eps: float = 0.0):
+        """``vc_set_sqp_infeasibility``: in-kernel infeasibility detection of the single-track fp64
+        SQP (csrc/st_sqp.hip).  On: a problem whose first QP has no feasible point ends with status
+        ``VC_INFEASIBLE`` (4); a later infeasible QP ends the SQP at the current iterate as before,
+        only sooner.  Either way ``sqp_farkas()`` returns the proof.  ``eps <= 0`` keeps the default
+        guard 1e-9.  Raises ``VcError``: VC_E_UNSUPPORTED on kinematic / cascaded / fp32 contexts,
+        VC_E_ARG when ``trust_Fx <= 0``."""
+        self._check(self.lib.vc_set_sqp_infeasibility(self._h, int(bool(on)), float(eps)))
+        self.detect_infeasible = bool(on)
+        self._last = None
+
+    def sqp_farkas(self, B: int | None = None):
+        """``vc_get_sqp_farkas``: ``(y[B, 12N - 3], qp_index[B])`` of the last solve -- rows in the
+        order of oracle/dyn_sqp.py ``dyn_qp``, ``qp_index`` the SQP iteration whose QP was certified
+        infeasible or -1 (``y``'s row is then zero).  Numpy arrays after a host-array solve, torch
+        tensors on the context's device after a device-tensor one.  Raises ``VcError`` when the
+        detection is off."""
+        last_B, dev = self._last if self._last is not None else (0, None)
+        B = last_B if B is None else int(B)
+        m = 12 * self.N - 3
+        if dev is not None:
+            import torch
+            y = torch.empty((B, m), dtype=torch.float64, device=dev)
+            qi = torch.empty((B,), dtype=torch.int32, device=dev)
+            ptrs, flags = (C.c_void_p(y.data_ptr()), C.c_void_p(qi.data_ptr())), _abi.VC_DEVICE_PTRS
+        else:
+            y = np.empty((B, m), np.float64)
+            qi = np.empty((B,), np.int32)
+            ptrs, flags = (C.c_void_p(y.ctypes.data), C.c_void_p(qi.ctypes.data)), _abi.VC_HOST_PTRS
+        self._check(self.lib.vc_get_sqp_farkas(self._h, B, ptrs[0], ptrs[1], flags))
+        return y, qi
 
     def synchronize(self):
         self._check(self.lib.vc_synchronize(self._h))
