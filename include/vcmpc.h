@@ -411,7 +411,8 @@ int vc_horizon(vc_ctx* ctx, int B, const void* x0, const void* xbar, double mpc_
 /* Plant step of RacingCar.drive: x64 <- transition(x64, u0, k(s), dt) in fp64 (the
  * reference's plant is an fp64 CasADi function; kinematic Euler, dynamic RK4), with
  * k from the track table.  x64[B][nx] fp64 in/out, u0[B][nu] context dtype;
- * x_ctx[B][nx] (context dtype, may be NULL) receives the new state for the next solve. */
+ * x_ctx[B][nx] (context dtype, may be NULL) receives the new state for the next solve.
+ * The plant alone: vc_qp.shift and the failure policy are vc_simulate's and do not act here. */
 int vc_drive(vc_ctx* ctx, int B, double* x64, const void* u0, double dt, void* x_ctx, int flags);
 
 /* `steps` closed-loop steps for B vehicles, all on the device (one HIP stream):

@@ -34,12 +34,12 @@ def _cfg(M):
     return cfg
 
 
-def _ctx(M, B=64, obstacles=None, solver=0):
+def _ctx(M, B=64, obstacles=None, solver=0, tyre="fiala"):
     from vcmpc import Context, _abi
     from vcmpc.config import make_params, load_config
     cfg = _cfg(M)
     cfg["qp"] = dict(cfg["qp"], solver=solver)
-    p = make_params(dyn_car=load_config("dynamic_car"), dyn_mpc=cfg, tyre="fiala", obstacles=obstacles)
+    p = make_params(dyn_car=load_config("dynamic_car"), dyn_mpc=cfg, tyre=tyre, obstacles=obstacles)
     return Context(model=_abi.VC_MODEL_CASCADED, N=N, max_batch=B, dtype=_abi.VC_F64, params=p)
 
 
@@ -140,20 +140,21 @@ def test_casc_ric_batch_properties(M, dyn_params):
     np.testing.assert_array_equal(r[2].cpu().numpy(), us)
 
 
+@pytest.mark.parametrize("tyre", ["fiala", "linear"])
 @pytest.mark.parametrize("M", [35, 40])
-def test_casc_ric_j_placement_bit_identical(M):
+def test_casc_ric_j_placement_bit_identical(M, tyre):
     """Round 5: M = 35 / 40 keep the stage Jacobians in LDS while the batch fits the machine at
     three workgroups per CU and in a global workspace beyond (four per CU; csrc/casc_ric.hip
     cr_launch): every problem of a 4,096 batch (global J) equals the same problem solved in LDS-J
-    chunks of 512 bit for bit (the whole batch: ADVICE r05)."""
+    chunks of 512 bit for bit (the whole batch: ADVICE r05), with either tyre model."""
     from vcmpc.workload import cascaded_batch
     B, CH = 4096, 512
-    d = cascaded_batch(B, M=M, seed=56)
-    with _ctx(M, B=B) as c:
+    d = cascaded_batch(B, M=M, seed=56, tyre=tyre)
+    with _ctx(M, B=B, tyre=tyre) as c:
         big = c.solve(d["x0"], d["kappa"], d["ds"], d["ubar"].copy(), diag=True)
         parts = [c.solve(d["x0"][i:i + CH], d["kappa"][i:i + CH], d["ds"][i:i + CH], d["ubar"][i:i + CH].copy(),
                          diag=True) for i in range(0, B, CH)]
     small = [np.concatenate([p[j] for p in parts]) for j in range(len(big))]
-    print(f"M={M}: solved {(big[3] == 0).mean():.4f} of {B}")
+    print(f"M={M} {tyre}: solved {(big[3] == 0).mean():.4f} of {B}")
     for a, b in zip(big, small):
         np.testing.assert_array_equal(a, b)

@@ -158,6 +158,62 @@ def test_horizon_dynamic_fp32(tracks):
         assert d.max() <= 1
 
 
+def test_horizon_dynamic_fp64(tracks):
+    """horizon_kernel<double, double, DYNAMIC>: ds bit-exact, kappa to the table tolerance (the
+    bars of test_horizon_kinematic_fp64), four starts whose horizon runs over the lap end.
+    Measured on an MI355X: max |kappa - kappa_oracle| = 0."""
+    pt, _ = tracks
+    B, N = 128, 20
+    rng = np.random.default_rng(16)
+    x0 = _dyn_states(B, pt.length, 16)
+    x0[:4, 4] = pt.length - rng.uniform(0, 2, 4)
+    xbar = np.ones((B, N, 8))
+    xbar[..., 0] = rng.uniform(3, 20, (B, N))
+    with _dyn_ctx(pt, B=B, N=N, f64=True) as c:
+        kap, ds = c.horizon(x0, xbar, MPC_DT)
+    worst = 0.0
+    for b in range(B):
+        ds_r, k_r = D.dyn_horizon_params(x0[b], xbar[b].T, MPC_DT, N, pt.k)
+        np.testing.assert_array_equal(ds[b], ds_r)
+        worst = max(worst, np.abs(kap[b] - k_r).max())
+    print(f"dynamic fp64 horizon: max |kappa - kappa_oracle| = {worst:.2e}")
+    assert worst < 1e-13
+    assert (x0[:4, 4] + ds[:4].sum(1) - ds[:4, -1] > pt.length).all()   # they do cross the lap end
+
+
+@pytest.mark.parametrize("Mh", [15, 40])
+def test_horizon_cascaded_fp64(tracks, Mh):
+    """horizon_kernel<double, double, CASCADED>: the single-track stages as above, then the
+    point-mass tail ds = ds_pm, s = cumsum(ds_pm) - ds[N-1] + s_traj[N-1] (cascaded_mpc.py:332-338)
+    against oracle/casc_sqp.py casc_horizon_params.  Four starts within 2 m of the lap end, so
+    that the tail's s wraps.  Measured on an MI355X: max |kappa - kappa_oracle| = 0, both tails."""
+    from oracle import casc_sqp as CS
+    from vcmpc import Context, _abi
+    from vcmpc.config import load_config, make_params
+    pt, _ = tracks
+    B, N = 64, 20
+    cfg = load_config("cascaded_mpc")
+    cfg["horizon_pm"] = Mh
+    ds_pm = float(cfg["ds_pm"])
+    rng = np.random.default_rng(17 + Mh)
+    x0 = _dyn_states(B, pt.length, 17 + Mh)
+    x0[:4, 4] = pt.length - rng.uniform(0, 2, 4)
+    xbar = np.ones((B, N + Mh, 8))
+    xbar[:, :N, 0] = rng.uniform(3, 20, (B, N))
+    p = make_params(dyn_car=load_config("dynamic_car"), dyn_mpc=cfg, tyre="fiala")
+    with Context(model=_abi.VC_MODEL_CASCADED, N=N, max_batch=B, dtype=_abi.VC_F64, params=p) as c:
+        c.set_track(pt)
+        kap, ds = c.horizon(x0, xbar, MPC_DT)
+    assert kap.shape == ds.shape == (B, N + Mh)
+    worst = 0.0
+    for b in range(B):
+        ds_r, k_r = CS.casc_horizon_params(x0[b], xbar[b].T, MPC_DT, N, Mh, ds_pm, pt.k)
+        np.testing.assert_array_equal(ds[b], ds_r)
+        worst = max(worst, np.abs(kap[b] - k_r).max())
+    print(f"cascaded fp64 horizon M={Mh}: max |kappa - kappa_oracle| = {worst:.2e}")
+    assert worst < 1e-13
+
+
 # -- plant --------------------------------------------------------------------------------------
 @pytest.mark.parametrize("tyre", ["fiala", "linear"])
 def test_drive_dynamic_fp64_plant(tracks, tyre):

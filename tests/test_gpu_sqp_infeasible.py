@@ -259,6 +259,30 @@ def test_fiala_tyre():
     _check_status_and_certificates(P, N, _run(N, True, "fiala"))
 
 
+def test_detection_global_j_bit_identical():
+    """Test 9: st_sqp_kernel<60, linear, JG = true, DET = true>.  P(60) tiled 32 times to B = 1024 is
+    beyond the 768 problems the LDS-J kernel takes (csrc/st_sqp.hip st_jg_pick), so the launch runs the
+    global-J kernel with the detection on.  J placement moves data, not arithmetic: every tile must
+    equal the 32-problem LDS-J run of test 1 bit for bit -- status, iters, u*, x*, u0, diag, the Farkas
+    vector and qp_index -- so a per-problem addressing error in the J or the Farkas workspace at any
+    problem index shows as a mismatch (the pattern of test_gpu_st_sqp.py
+    test_st_sqp_j_placement_bit_identical).  Measured on an MI355X: identical; 448 solved and 576
+    certified (18 per tile) of 1024."""
+    N, T = 60, 32
+    small = _run(N, True)
+    d = {k: np.ascontiguousarray(np.concatenate([v] * T)) for k, v in _problems(N)["d"].items()}
+    assert len(d["x0"]) == T * B > 768
+    with _ctx(N, True, max_batch=T * B) as c:
+        big = c.solve(d["x0"], d["kappa"], d["ds"], d["ubar"].copy(), diag=True)
+        y, qi = c.sqp_farkas()
+    big = tuple(big) + (y, qi)
+    print(f"N={N} B={T * B} global J + detection: status counts {np.bincount(big[3], minlength=5).tolist()}, "
+          f"certified {int((qi >= 0).sum())}")
+    assert (small[3] == 4).sum() == 18   # the tiles carry certificates to compare
+    for a, s in zip(big, small):
+        np.testing.assert_array_equal(a, np.concatenate([s] * T))
+
+
 def test_controller_config_key_enables_detection():
     """Test 8: `qp.detect_infeasible` of the single-track controller config turns the detection on
     (default off); a step whose first QP is certified is counted and restarts neutrally like every

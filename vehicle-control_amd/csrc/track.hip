@@ -154,7 +154,9 @@ __global__ void drive_kernel(ModelArgs m, TrackTable tt, double* x64, const T* u
     for (int k = 0; k < NS; ++k)
 #pragma unroll
       for (int i = 0; i < NX; ++i) xbar[((size_t)b * NS + k) * NX + i] = T(xn[i]);
-  } else if (m.shift && MODEL != VC_MODEL_CASCADED) {
+  } else if (status && m.shift && MODEL != VC_MODEL_CASCADED) {
+    // vc_simulate only (status set): the public vc_drive passes no warm-start buffers, whatever
+    // vc_qp.shift says.
     // shifted warm start: the plan one stage on (single shooting re-rolls the warm-start inputs
     // from the new state; unshifted, they lag one step and over a 40 m kinematic horizon the
     // rollout crosses the spatial model's eps = +-pi/2 singularity, scripts/kin_shift_test.py)
