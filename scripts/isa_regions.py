@@ -1,0 +1,63 @@
+"""Static instruction counts of the fused kinematic kernel's regions between section stamps.
+
+Input: the timing build's device assembly,
+    hipcc --cuda-device-only -S -DVC_TIMING -O3 --offload-arch=gfx950 -Iinclude -Ivehicle-control_amd/csrc \
+        vehicle-control_amd/csrc/kin_ltv.hip -o kin_ltv_timing.s
+The kernel's text is split at each s_memtime (one per VC_TSTAMP / VC_TACC, in program order); each
+region is labelled with the source line of the stamp that opens it (from the .loc lines, if the
+assembly has them) and counted by instruction class.  Counts are static: both arms of a uniform
+branch inside a region are in it, and a loop body counts once.
+
+usage: python scripts/isa_regions.py kin_ltv_timing.s [min_instr]
+"""
+import re
+import sys
+
+CLASSES = [
+    ("f64", re.compile(r"^v_\w+_f64")),
+    ("v_cndmask", re.compile(r"^v_cndmask")),
+    ("agpr mov", re.compile(r"^v_accvgpr_(read|write|mov)")),
+    ("lane ops", re.compile(r"^(v_readlane|v_writelane|v_readfirstlane|ds_bpermute|ds_permute|ds_swizzle)|\b(row_shr|row_shl|row_bcast|quad_perm|row_ror|wave_sh)")),
+    ("ds_read", re.compile(r"^ds_read")),
+    ("ds_write", re.compile(r"^ds_write")),
+    ("mfma", re.compile(r"^v_mfma")),
+    ("s_waitcnt", re.compile(r"^s_waitcnt")),
+]
+
+
+def main():
+    path = sys.argv[1]
+    min_instr = int(sys.argv[2]) if len(sys.argv) > 2 else 0
+    lines = open(path).read().split("\n")
+    start = next(i for i, l in enumerate(lines) if re.match(r"^_ZN2vc14kin_ltv_kernel\w*:", l))
+    end = next(i for i in range(start, len(lines)) if lines[i].startswith(".Lfunc_end"))
+    regions, cur, loc = [], {"open": "entry", "n": 0}, "?"
+    for l in lines[start + 1:end]:
+        t = l.strip()
+        m = re.match(r"\.loc\s+\d+\s+(\d+)", t)
+        if m:
+            loc = m.group(1)
+            continue
+        if not t or t.startswith((";", ".", "//")) or t.endswith(":"):
+            continue
+        if t.startswith("s_memtime"):
+            regions.append(cur)
+            cur = {"open": f"line {loc}", "n": 0}
+            continue
+        cur["n"] += 1
+        for name, rx in CLASSES:
+            if rx.search(t):
+                cur[name] = cur.get(name, 0) + 1
+    regions.append(cur)
+    hdr = ["#", "opened at", "instr"] + [c for c, _ in CLASSES]
+    print("| " + " | ".join(hdr) + " |")
+    print("|" + "---|" * len(hdr))
+    for i, r in enumerate(regions):
+        if r["n"] < min_instr:
+            continue
+        print("| " + " | ".join([str(i), r["open"], str(r["n"])] + [str(r.get(c, 0)) for c, _ in CLASSES]) + " |")
+    print(f"total instructions {sum(r['n'] for r in regions)}, stamps {len(regions) - 1}")
+
+
+if __name__ == "__main__":
+    main()

@@ -18,7 +18,8 @@ from vcmpc.workload import kinematic_batch  # noqa: E402
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
 tol = float(sys.argv[2]) if len(sys.argv) > 2 else 1e-10
 names = ["S1 rollout", "setup", "resid", "build", "chol", "solve", "pol fact", "polish", "out", "S2 jac", "S3 sens", "S4 hess",
-         "pol AL", "AL passes", "upd rounds", "upd cyc", "drop rounds", "early fail", "carry rm", "carry add", "r0 change"]
+         "pol AL", "AL passes", "upd rounds", "upd cyc", "drop rounds", "early fail", "carry rm", "carry add", "r0 change",
+         "step", "total"]
 dev = torch.device("cuda:0")
 d = kinematic_batch(B, seed=31)
 t = {k: torch.from_numpy(v).to(dev) for k, v in d.items()}
@@ -44,12 +45,18 @@ with Context(N=20, max_batch=B, params=p) as c:
     its = it.cpu().numpy().astype(float)
     cyc = dg[:, 4:]
     # pol fact (slot 6) and pol AL (12) are parts of polish (7); slot 13 counts AL passes
-    tot = cyc[:, :12].sum(1) - cyc[:, 6]
+    # step (21): the Mehrotra passes outside the solves; total (22): the whole kernel, first to last instruction
+    tot = cyc[:, :12].sum(1) - cyc[:, 6] + cyc[:, names.index("step")]
+    whole = cyc[:, names.index("total")]
     print(f"B={B} tol={tol:g}: solved {(st.cpu().numpy() == 0).mean():.4f} iters mean {its.mean():.2f} max {its.max():.0f} "
           f"polish rounds mean {dg[:, 3].mean():.2f}")
     print(f"  total stamped cycles/problem: mean {tot.mean():.0f}  max {tot.max():.0f}")
+    print(f"  whole-kernel cycles/problem:  mean {whole.mean():.0f}  max {whole.max():.0f}")
+    una = whole - tot
+    print(f"  unaccounted (whole - slots):  mean {una.mean():.0f}  ({100 * una.mean() / whole.mean():.1f} % of whole)  "
+          f"slowest problem {una[tot.argmax()]:.0f}")
     for i, nm in enumerate(names):
-        per_it = cyc[:, i].sum() / max(its.sum(), 1) if nm in ("resid", "build", "chol", "solve") else float("nan")
+        per_it = cyc[:, i].sum() / max(its.sum(), 1) if nm in ("resid", "build", "chol", "solve", "step") else float("nan")
         print(f"  {nm:10s} mean {cyc[:, i].mean():10.0f}  ({100 * cyc[:, i].mean() / tot.mean():5.1f} %)  per IPM iter {per_it:9.0f}"
               f"   slowest problem {cyc[tot.argmax(), i]:10.0f}")
     # the launch ends with its slowest problem (one wave per SIMD at B = 1024): where the tail comes from
@@ -85,4 +92,4 @@ with Context(N=20, max_batch=B, params=p) as c:
         print("  early-fail problems' first change: " + ", ".join(f"{int(b)}: {kinds[(r0[b] - 1) % 3]} / {tap[(r0[b] - 1) // 3]}"
                                                           for b in np.nonzero(ef)[0]))
     if os.environ.get("SEC_DUMP"):  # per-problem arrays for offline tail analysis
-        np.savez(os.environ["SEC_DUMP"], cyc=cyc, its=its, rounds=dg[:, 3], tot=tot)
+        np.savez(os.environ["SEC_DUMP"], cyc=cyc, its=its, rounds=dg[:, 3], tot=tot, whole=whole)

@@ -187,7 +187,10 @@ __device__ __forceinline__ lds_cdouble* lds_opaque(const double* p) {
 // T_CFAIL 1 after a failed early attempt, T_CRM / T_CADD how many bounds and rows the final attempt's
 // first set drops / adds against the early attempt's last factored one (a study of carrying that factor);
 // T_R0CHG the early attempt's first change: 1 + (0 box add, 1 row add, 2 drop) + 3 x its side's Tapia state
-enum { T_SWEEP = 0, T_SETUP, T_RESID, T_BUILD, T_CHOL, T_SOLVE, T_UPDATE, T_POLISH, T_OUT, T_S2, T_S3, T_S4, T_PAL, T_PPASS, T_NUPD, T_UCYC, T_NDROP, T_CFAIL, T_CRM, T_CADD, T_R0CHG, T_NSLOT };
+// T_STEP: the two Mehrotra passes outside chol_solve (reciprocals, right-hand sides, G products, step
+// lengths, update); T_TOTAL: the whole kernel, first to last instruction (what no slot covers shows
+// up as total minus the slots: scripts/section_timing.py's "unaccounted" row)
+enum { T_SWEEP = 0, T_SETUP, T_RESID, T_BUILD, T_CHOL, T_SOLVE, T_UPDATE, T_POLISH, T_OUT, T_S2, T_S3, T_S4, T_PAL, T_PPASS, T_NUPD, T_UCYC, T_NDROP, T_CFAIL, T_CRM, T_CADD, T_R0CHG, T_STEP, T_TOTAL, T_NSLOT };
 
 
 template <int N>
@@ -836,6 +839,10 @@ __global__ __launch_bounds__(64) void kin_ltv_kernel(KinLtvArgs A) {
   const int b = xcd_problem(blockIdx.x, A.B);
   if (b >= A.B) return;
   const vc_kin_mpc& W = A.w;
+#ifdef VC_TIMING
+  uint64_t tacc[T_NSLOT] = {};
+#endif
+  VC_TSTAMP(t_all0)
 
   // ---- load inputs (coalesced) -------------------------------------------
   if (lane < n) s.ub[lane] = A.ubar[(size_t)b * n + lane];
@@ -849,9 +856,6 @@ __global__ __launch_bounds__(64) void kin_ltv_kernel(KinLtvArgs A) {
   if (lane == 0) s.Lc[Smem<N>::LC_ZERO] = 0.0;
   wave_sync();
 
-#ifdef VC_TIMING
-  uint64_t tacc[T_NSLOT] = {};
-#endif
   VC_TSTAMP(t_sweep0)
   // ---- predict + linearize + condense ------------------------------------------
   // S1 serial rollout (uniform across lanes; the only serial transcendental
@@ -898,31 +902,43 @@ __global__ __launch_bounds__(64) void kin_ltv_kernel(KinLtvArgs A) {
         f[4] = tdl * rc - kap;
         f[5] = q;
       }
-      double mine = 0.0;
 #pragma unroll
-      for (int i = 0; i < KIN_NX; ++i) {
-        x[i] += h * f[i];
-        finite = finite && isfinite(x[i]);
-        mine = (i == lane) ? x[i] : mine;
+      for (int i = 0; i < KIN_NX; ++i) x[i] += h * f[i];
+      // the state is uniform: one lane stores it (a per-lane select chain over the six
+      // components sat on the serial path)
+      if (lane == 0) {
+#pragma unroll
+        for (int i = 0; i < KIN_NX; ++i) s.xb[k + 1][i] = x[i];
       }
-      s.xb[k + 1][lane < KIN_NX ? lane : KIN_NX] = mine;  // xb rows padded: col KIN_NX is a dummy
-      // ey_{k+1} cost weight and linear term: stage (deviation + boundary,
-      // kinematic_mpc.py:110-122) or terminal (:152-154)
-      const double ey = x[3];
-      double cw, lin;
-      if (k + 1 < N) {
-        const double hs = s.ds[k + 1];
-        cw = W.w_dev * hs;
-        lin = W.w_dev * hs * ey;
-        if (ey < W.ey_min) { cw += W.w_b * hs; lin += W.w_b * hs * (ey - W.ey_min); }
-        if (ey > W.ey_max) { cw += W.w_b * hs; lin += W.w_b * hs * (ey - W.ey_max); }
-      } else {
-        cw = W.w_ey;
-        lin = W.w_ey * ey;
-      }
-      s.vc[k] = 2.0 * cw;
-      s.vz[k] = 2.0 * lin;
     }
+    // x += h f keeps a non-finite component non-finite, so the final state decides
+#pragma unroll
+    for (int i = 0; i < KIN_NX; ++i) finite = finite && isfinite(x[i]);
+  }
+  wave_sync();
+  // ey_{k+1} cost weight and linear term, lane k for stage k + 1 (off the rollout's chain): stage
+  // (deviation + boundary, kinematic_mpc.py:110-122) or terminal (:152-154)
+  if (lane < N) {
+    const double ey = s.xb[lane + 1][3];
+    double cw, lin;
+    if (lane + 1 < N) {
+      // cw = w_dev hs (+ w_b hs), lin = w_dev hs ey (+ w_b hs (ey - bound)) with every rounding
+      // spelled out (explicit fma, the boundary weight opaque to the contraction pass): u* stays
+      // bit-identical to the serial form, whose roundings these are (tests/test_gpu_kin_step.py)
+      const double hs = s.ds[lane + 1];
+      const double td = W.w_dev * hs;
+      double tb = W.w_b * hs;
+      asm volatile("" : "+v"(tb));
+      cw = td;
+      lin = ey * td;
+      if (ey < W.ey_min) { cw = __builtin_fma(W.w_dev, hs, tb); lin = __builtin_fma(ey - W.ey_min, tb, lin); }
+      if (ey > W.ey_max) { cw = cw + tb; lin = __builtin_fma(ey - W.ey_max, tb, lin); }
+    } else {
+      cw = W.w_ey;
+      lin = W.w_ey * ey;
+    }
+    s.vc[lane] = 2.0 * cw;
+    s.vz[lane] = 2.0 * lin;
   }
   wave_sync();
   VC_TACC(T_SWEEP, t_sweep0)
@@ -1196,6 +1212,10 @@ __global__ __launch_bounds__(64) void kin_ltv_kernel(KinLtvArgs A) {
         near = res <= 1e-6 * scale && mu <= tol;
         break;
       }
+#ifdef VC_TIMING
+      const uint64_t t_sol_before = tacc[T_SOLVE];
+#endif
+      VC_TSTAMP(t_step0)
       // inverse slacks / multipliers of this iteration (0 on absent sides): the two passes
       // divide by them 16 times, and the fraction to the boundary min over -v/dv (dv < 0)
       // is 1 / max over -dv (1/v)
@@ -1267,6 +1287,10 @@ __global__ __launch_bounds__(64) void kin_ltv_kernel(KinLtvArgs A) {
           rd *= om; rlo_b *= om; rhi_b *= om; rlo_c *= om; rhi_c *= om;
         }
       }
+      VC_TACC(T_STEP, t_step0)
+#ifdef VC_TIMING
+      tacc[T_STEP] -= tacc[T_SOLVE] - t_sol_before;
+#endif
     }
   }
 
@@ -1586,34 +1610,58 @@ __global__ __launch_bounds__(64) void kin_ltv_kernel(KinLtvArgs A) {
       A.diag[(size_t)b * DS + 3] = double(rounds);
     }
   }
-  // x* = xbar + G dz via the linearised recursion, lanes 0..5 own components
-  double dx[KIN_NX] = {0, 0, 0, 0, 0, 0};
-  double* xo = A.x_out + (size_t)b * (N + 1) * KIN_NX;
-  if (lane < KIN_NX) xo[lane] = s.xb[0][lane];
-#pragma unroll 1
-  for (int k = 0; k < N; ++k) {
+  // x* = xbar + dx, dx the linearised recursion dx_{k+1} = A_k dx_k + B_k dz_k from dx_0 = 0.  Only
+  // (dey, depsi) form a serial chain (two states, fed by ddelta); the rest is lane-parallel:
+  //   dv_k, ddelta_k (k = 1..N-1) = G z, one grow_dot for all stages, left in LDS (vc / vz above z);
+  //   the chain, uniform over the lanes, which drops stage k's pair into lane k;
+  //   then lane k: dq_k, one recursion step from stage k to k + 1 for v and delta (stage N has
+  //   no row in G), and dt_{k+1} as the prefix sum of h_k dq_k;
+  //   xbar + dx staged through s.xb and stored coalesced.
+  // (The 20-stage recursion on all six states, every lane the same ~25 flops, 15 LDS reads, a six-way
+  // lane select and a store per stage, was 11.7 K cycles of every problem.)
+  {
+    const double y = grow_dot<N>(s, lane);  // s.vz = z
+    // dv_k -> vc[k], ddelta_k -> vz[n + k], k = 0..N-1 (0 at k = 0, from lanes NC and NC + 1)
+    const int slot = lane < N - 1 ? 64 + lane + 1
+                                  : (lane < NC ? n + (lane - (N - 1)) + 1 : (lane == NC ? 64 : (lane == NC + 1 ? n : 127)));
+    wave_sync();
+    s.tb2[slot] = y;  // tb2 = vz (0..63) followed by vc (64..127); slot 127: dummy
+    wave_sync();
+    double ey = 0.0, ep = 0.0, eyk = 0.0, epk = 0.0;
+#pragma unroll 4
+    for (int k = 0; k < N; ++k) {
+      const double h = s.ds[k], dd = s.vz[n + k];
+      eyk = lane_put(eyk, ey, k);
+      epk = lane_put(epk, ep, k);
+      const double ney = ey + h * (s.jac[k][4] * ey + s.jac[k][5] * ep);
+      const double nep = ep + h * (s.jac[k][6] * dd + s.jac[k][7] * ey + s.jac[k][8] * ep);
+      ey = ney; ep = nep;
+    }
+    eyk = lane_put(eyk, ey, N);
+    epk = lane_put(epk, ep, N);
+    const double eyn = __shfl_down(eyk, 1), epn = __shfl_down(epk, 1);  // stage k + 1's pair
+    const int k = lane < N ? lane : 0;
     const double q = s.jac[k][0], qv = s.jac[k][1], qey = s.jac[k][2], qep = s.jac[k][3];
     const double h = s.ds[k], a = s.ub[2 * k], w = s.ub[2 * k + 1];
     const double da = s.vz[2 * k], dw = s.vz[2 * k + 1];
-    const double dq = qv * dx[0] + qey * dx[3] + qep * dx[4];
-    double nx[KIN_NX];
-    nx[0] = dx[0] + h * (a * dq + q * da);
-    nx[1] = dx[1] + h * (w * dq + q * dw);
-    nx[2] = dx[2];
-    nx[3] = dx[3] + h * (s.jac[k][4] * dx[3] + s.jac[k][5] * dx[4]);
-    nx[4] = dx[4] + h * (s.jac[k][6] * dx[1] + s.jac[k][7] * dx[3] + s.jac[k][8] * dx[4]);
-    nx[5] = dx[5] + h * dq;
-    double mine = 0.0;
-#pragma unroll
-    for (int i = 0; i < KIN_NX; ++i) {
-      dx[i] = nx[i];
-      if (i == lane) mine = nx[i];
+    const double dv = s.vc[k], dd = s.vz[n + k];
+    const double dq = qv * dv + qey * eyk + qep * epk;
+    const double dt = wave_prefix(lane < N ? h * dq : 0.0, lane);  // dt_{k+1}
+    wave_sync();
+    if (lane < N) {
+      double* xr = s.xb[k + 1];
+      xr[0] += dv + h * (a * dq + q * da);
+      xr[1] += dd + h * (w * dq + q * dw);
+      xr[3] += eyn;
+      xr[4] += epn;
+      xr[5] += dt;
     }
-    if (lane < KIN_NX) xo[(k + 1) * KIN_NX + lane] = s.xb[k + 1][lane] + mine;
+    wave_sync();
+    double* xo = A.x_out + (size_t)b * (N + 1) * KIN_NX;
+    for (int i = lane; i < (N + 1) * KIN_NX; i += 64) xo[i] = s.xb[i / KIN_NX][i % KIN_NX];
   }
-  // (reading each step's LDS operands a step ahead, S3's pattern, measured equal: C2 0.2090 vs
-  // 0.2097 ms, profiles/r06/kin_ab/kin_polish_ab_c2_r06z.log -- the section is not LDS-latency bound)
   VC_TACC(T_OUT, t_out0)
+  VC_TACC(T_TOTAL, t_all0)
 #ifdef VC_TIMING
   // timing builds: diag is [B][4 + T_NSLOT]
   if (A.diag && lane < T_NSLOT) {
