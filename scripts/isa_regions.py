@@ -5,7 +5,9 @@ Input: the timing build's device assembly,
         vehicle-control_amd/csrc/kin_ltv.hip -o kin_ltv_timing.s
 The kernel's text is split at each s_memtime (one per VC_TSTAMP / VC_TACC, in program order); each
 region is labelled with the source line of the stamp that opens it (from the .loc lines, if the
-assembly has them) and counted by instruction class.  Counts are static: both arms of a uniform
+assembly has them) and counted by instruction class -- the last three columns are the scalar
+instructions (s_* other than s_waitcnt / s_nop), the s_nop padding, and the vector instructions no
+other class names.  Counts are static: both arms of a uniform
 branch inside a region are in it, and a loop body counts once.
 
 usage: python scripts/isa_regions.py kin_ltv_timing.s [min_instr]
@@ -22,7 +24,15 @@ CLASSES = [
     ("ds_write", re.compile(r"^ds_write")),
     ("mfma", re.compile(r"^v_mfma")),
     ("s_waitcnt", re.compile(r"^s_waitcnt")),
+    # the scalar unit's own work, its padding, and whatever vector work no class above names: a cut
+    # that trades vector instructions for scalar ones (a lane set decided by s_mov instead of
+    # v_cmp) shows as such instead of as a smaller "instr" alone
+    ("scalar", re.compile(r"^s_(?!waitcnt|nop)")),
+    ("s_nop", re.compile(r"^s_nop")),
+    ("other vec", None),
 ]
+# "other vec": v_* / ds_* / memory instructions matched by no class above
+VECTOR = re.compile(r"^(v_|ds_|global_|flat_|buffer_|scratch_)")
 
 
 def main():
@@ -45,9 +55,13 @@ def main():
             cur = {"open": f"line {loc}", "n": 0}
             continue
         cur["n"] += 1
+        hit = False
         for name, rx in CLASSES:
-            if rx.search(t):
+            if rx is not None and rx.search(t):
                 cur[name] = cur.get(name, 0) + 1
+                hit = True
+        if not hit and VECTOR.match(t):
+            cur["other vec"] = cur.get("other vec", 0) + 1
     regions.append(cur)
     hdr = ["#", "opened at", "instr"] + [c for c, _ in CLASSES]
     print("| " + " | ".join(hdr) + " |")

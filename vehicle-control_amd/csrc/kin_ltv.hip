@@ -148,6 +148,29 @@ __device__ __forceinline__ int lane_opaque(int lane) {
   asm volatile("" : "+v"(lane));
   return lane;
 }
+// `in` on lanes lo..hi-1, the constant `other` on the others, for a lane range known at compile time
+// (wave64 only, like the rest of this file -- one 64-lane wave per problem: the mask is the 64-bit
+// VCC pair).  lo and hi - lo must fold to constants in 0..63 once the caller is inlined and its
+// loops unrolled -- the "i" constraints reject anything else when the kernel is compiled (s_bfm_b64
+// reads six bits of each: a width of 64 would give the empty set).  The mask is made by ONE scalar
+// instruction inside the same asm statement as the v_cndmask that reads it, so nothing outlives the
+// statement.  The trap this avoids: left to the compiler as a compare on an opaque lane, or handed
+// to the asm as an "s" operand, the 40 masks of an unrolled factorisation are loop invariants that
+// machine LICM hoists out of the interior-point loop and spills through VGPR lanes (v_writelane /
+// v_readlane, each behind an s_nop).  With one wave per SIMD a scalar instruction is not free
+// either, it takes the wave's issue slot like a vector one (two s_mov_b32 of literal halves per
+// mask measured slower than the compares they replaced: DESIGN 3.1 round 8), hence one s_bfm_b64.
+// `other` goes through a v_mov: VCC and a literal would be two constant-bus reads in one
+// instruction, one more than gfx9 encodes.
+__device__ __forceinline__ uint32_t lane_range_pick(uint32_t in, int other, int lo, int hi) {
+  uint32_t r;
+  asm("s_bfm_b64 vcc, %3, %4\n\t"
+      "v_mov_b32_e32 %0, %2\n\tv_cndmask_b32_e32 %0, %0, %1, vcc"
+      : "=&v"(r)
+      : "v"(in), "i"(other), "i"(hi - lo), "i"(lo)
+      : "vcc");
+  return r;
+}
 // compiler-only memory barrier: stops LICM from hoisting the (loop-invariant) LDS
 // reads of G / the factor out of the solver loops into thousands of live registers
 __device__ __forceinline__ void no_hoist() { asm volatile("" ::: "memory"); }
@@ -581,9 +604,11 @@ __device__ __forceinline__ void build_normal_mfma(double (&Mr)[Dims<N>::n], Smem
 // Pivot steps: two columns per step -- the 2x2 diagonal block comes from lanes k, k+1 by
 // readlane, both pivots are taken in registers (rsq_nr), both columns published to LDS, and one
 // LDS round trip serves the rank-2 update.  Software-pipelined: the pivot block k+2, k+3 depends
-// only on the lookahead columns (chunk 0 of step k's update), so its chain -- readlanes, two
-// rsq, the column scaling and its stores -- is split in three parts placed in the fence regions
-// of step k's update chunks 1, 2, 3, where the scheduler interleaves it with independent FMAs.
+// only on the lookahead columns k+2, k+3 of step k's update, which take columns k, k+1 from the
+// lanes' registers by readlane instead of from LDS (the same values: the chain skips the store /
+// load round trip), so its chain -- readlanes, two rsq, the column scaling and its stores -- is
+// split in three parts: the first right behind the lookahead update, the others in the fence
+// regions of step k's update chunks, where the scheduler interleaves them with independent FMAs.
 // (A row-per-lane unblocked version of the same steps was the round-2/3 factorisation; the
 // second pivot from the block's determinant, both rsq chains in parallel, measured no gain in
 // round 6: the steps are bound by issue, not by the pivot chain.)
@@ -598,6 +623,16 @@ __device__ bool factor_blocked(double (&Mr)[Dims<N>::n], d4 (&acc)[Tiles<N>::NT]
   const int lr = lane >> 4, lc = lane & 15, myI = lane >> 4;
   bool ok = true;
   double pa, pb, pc, pi1, pl21, pi2;  // chain state of the pending pivot block
+  // Lc[lc_base(k) + lane] = v on lanes k..n-1, the dummy slot on the others (branch-free): one select
+  // between this lane's byte offset and column k's offset of the dummy slot, the column base in the
+  // store's offset field
+  using lds_double = __attribute__((address_space(3))) double;
+  using lds_char = __attribute__((address_space(3))) char;
+  const uint32_t lane8 = 8u * uint32_t(lane);
+  auto col_store = [&](int k, double v) {
+    const uint32_t off = lane_range_pick(lane8, 8 * (DUMMY - lc_base<n>(k)), k, n);
+    *(lds_double*)((lds_char*)&s.Lc[lc_base<n>(k)] + off) = v;
+  };
   auto part = [&](int p, int k) {
     if (p == 0) {
       pa = lane_bcast(Mr[k], k);
@@ -614,8 +649,8 @@ __device__ bool factor_blocked(double (&Mr)[Dims<N>::n], d4 (&acc)[Tiles<N>::NT]
       const double y = fma(-x, pl21, Mr[k + 1]) * pi2;
       Mr[k] = x;
       Mr[k + 1] = y;
-      s.Lc[lane >= k && lane < n ? lc_base<n>(k) + lane : DUMMY] = x;
-      s.Lc[lane >= k + 1 && lane < n ? lc_base<n>(k + 1) + lane : DUMMY] = y;
+      col_store(k, x);
+      col_store(k + 1, y);
       s.dinv[k] = pi1;
       s.dinv[k + 1] = pi2;
     }
@@ -658,12 +693,10 @@ __device__ bool factor_blocked(double (&Mr)[Dims<N>::n], d4 (&acc)[Tiles<N>::NT]
       wave_sync();  // columns k, k+1 visible
       fence();
       const double x = Mr[k], y = Mr[k + 1];
-      Mr[k] = lane > k ? x : 0.0;
-      Mr[k + 1] = lane > k + 1 ? y : 0.0;
       const double* cA = &s.Lc[lc_base<n>(k)];
       const double* cB = &s.Lc[lc_base<n>(k + 1)];
       constexpr int CH = KIN_PANEL_CH;
-      const int J0 = k + 2, NCH = (c1 - J0 + CH - 1) / CH;
+      const int J0 = k + 4, NCH = (c1 - J0 + CH - 1) / CH;
       double u0[2][CH], u1[2][CH];
       auto load = [&](int ch, int buf) {
 #pragma unroll
@@ -673,7 +706,14 @@ __device__ bool factor_blocked(double (&Mr)[Dims<N>::n], d4 (&acc)[Tiles<N>::NT]
           u1[buf][q] = j < c1 ? cB[j] : 0.0;
         }
       };
-      load(0, 0);
+      if (NCH > 0) load(0, 0);
+      // the lookahead columns k+2, k+3 take their factors L[j][k], L[j][k+1] from lanes j's x, y by
+      // readlane -- the values the LDS columns hold -- so the next pivot block's chain does not
+      // wait for this step's column stores to come back from LDS
+#pragma unroll
+      for (int j = k + 2; j < k + 4; ++j)
+        Mr[j] = fma(-y, lane_bcast(y, j), fma(-x, lane_bcast(x, j), Mr[j]));
+      part(0, k + 2);
 #pragma unroll
       for (int ch = 0; ch < NCH; ++ch) {
         if (ch + 1 < NCH) load(ch + 1, (ch + 1) & 1);
@@ -683,17 +723,15 @@ __device__ bool factor_blocked(double (&Mr)[Dims<N>::n], d4 (&acc)[Tiles<N>::NT]
           const int j = J0 + ch * CH + q;
           if (j < c1) Mr[j] = fma(-y, u1[ch & 1][q], fma(-x, u0[ch & 1][q], Mr[j]));
         }
-        if (ch >= 1 && ch <= 3) part(ch - 1, k + 2);
+        if (ch + 1 < 3) part(ch + 1, k + 2);
         fence();
       }
 #pragma unroll
-      for (int pp = NCH - 1; pp < 3; ++pp) {
-        part(pp < 0 ? 0 : pp, k + 2);
+      for (int pp = NCH + 1; pp < 3; ++pp) {
+        part(pp, k + 2);
         fence();
       }
     }
-    Mr[c1 - 2] = lane > c1 - 2 ? Mr[c1 - 2] : 0.0;
-    Mr[c1 - 1] = lane > c1 - 1 ? Mr[c1 - 1] : 0.0;
     wave_sync();  // the panel's factor columns visible
     // ---- rank-W update of the tiles right of the panel on the matrix cores
     if (p + 1 < NB) {
@@ -720,6 +758,14 @@ __device__ bool factor_blocked(double (&Mr)[Dims<N>::n], d4 (&acc)[Tiles<N>::NT]
       }
     }
   }
+  // the row registers zero on and above the diagonal (what the solves' forward sweeps rely on), in
+  // one pass once every column's update has read its unmasked value.  Written inside the pivot
+  // steps, the compiler computed the 40 compares there, kept the masks alive to the selects it sank
+  // down here anyway, and spilled 18 mask pairs through VGPR lanes on the way.  The lane is
+  // laundered per column: with one opaque lane for the whole pass the kernel spills 20 bytes per
+  // lane to scratch.
+#pragma unroll
+  for (int k = 0; k < n; ++k) Mr[k] = lane_opaque(lane) > k ? Mr[k] : 0.0;
   store_rows<N>(Mr, s, lane);
   wave_sync();  // factor and inverse pivots visible to the solves
   return ok;
