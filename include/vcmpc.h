@@ -50,7 +50,8 @@
  *   - Return value: 0 on success, a negative VC_E* code on an API or HIP error
  *     (message via vc_last_error).  Per-problem outcomes are reported in status[b]
  *     (VC_SOLVED, VC_MAX_ITER, VC_NONFINITE, VC_OUT_OF_DOMAIN, and VC_INFEASIBLE where
- *     vc_set_infeasibility / vc_set_sqp_infeasibility turned the detection on); no
+ *     vc_set_infeasibility / vc_set_sqp_infeasibility / vc_set_casc_infeasibility turned the
+ *     detection on); no
  *     exception-style failure, unlike the
  *     reference simulator's catch-all (simulation/racing.py:416-423).
  *   - Threading: one context per device per host thread; calls on one context
@@ -83,7 +84,9 @@ enum vc_tyre { VC_TYRE_FIALA = 0, VC_TYRE_LINEAR = 1 };
  * Farkas vector (vc_get_farkas).  u* / x* / u0 are the warm start and its prediction (dz = 0).
  * Never reported unless the detection is on: such a QP then ends VC_MAX_ITER as before.
  * Single-track fp64 SQP with vc_set_sqp_infeasibility on: the first QP of the SQP has no feasible
- * point (vc_get_sqp_farkas); u* / x* / u0 are the warm start and its rollout. */
+ * point (vc_get_sqp_farkas); u* / x* / u0 are the warm start and its rollout.
+ * Cascaded fp64 SQP (stagewise kernel) with vc_set_casc_infeasibility on: the same over the
+ * N + horizon_pm stages (vc_get_casc_farkas). */
 enum vc_status { VC_SOLVED = 0, VC_MAX_ITER = 1, VC_NONFINITE = 2, VC_OUT_OF_DOMAIN = 3, VC_INFEASIBLE = 4 };
 enum vc_error {
   VC_OK = 0,
@@ -292,6 +295,40 @@ int vc_set_sqp_infeasibility(vc_ctx* ctx, int on, double eps);
  * exceeds the last solve's batch. */
 int vc_get_sqp_farkas(vc_ctx* ctx, int B, void* y, int32_t* qp_index, int flags);
 
+/* Infeasibility detection of the cascaded SQP (ABI 13, additive; VC_MODEL_CASCADED, VC_F64, the
+ * stagewise kernel casc_ric.hip: N = 20 with horizon_pm = 15 / 25 / 35 / 40, both tyres, either J
+ * placement).  on != 0: every QP of the SQP is tested inside its interior point in every iteration
+ * from the second, ahead of the exits on a breakdown, exactly as vc_set_sqp_infeasibility does for
+ * the single track.  The rows are those of oracle/casc_sqp.py casc_qp, m = 12N - 3 + 6 horizon_pm,
+ * in the scaled variables dz = (dFx / S, dw) for k < N and (dFx / S, dFy / S) for the point mass,
+ * S = fx_scale.  The Fx trust region, the (trust-tightened) w box and the point mass's Fx / Fy trust
+ * rows bound every feasible dz:
+ *     |dz|_1 <= R = sum_{k<N} [ trust_Fx / S + max(0, up_k, dn_k) ] + sum_{m<horizon_pm} 2 trust_Fx / S,
+ * and with y = lam / |lam|_1
+ *     d'y + R |C'y|_inf < -eps (1 + the magnitude of the summed terms)   =>   no dz has C dz <= d
+ * (C'y condensed onto the 2 (N + horizon_pm) inputs through the open-loop dynamics: the single-track
+ * steps, the switching map and the point-mass steps; eps <= 0 keeps 1e-9).
+ *   - certified in SQP iteration 0: the problem ends at once with status VC_INFEASIBLE, u* / x* / u0
+ *     the warm start and its rollout, iters the count so far, diag[2] bit 32;
+ *   - certified in a later SQP iteration: the step is refused and the SQP ends at the current iterate
+ *     exactly as when such a QP runs to max_iter (diag[2] bit 16), only sooner; status comes from the
+ *     earlier QPs, diag[2] has bits 16 and 32.
+ * Default off: the context then behaves exactly as before.  vc_condense is not affected.
+ * VC_E_UNSUPPORTED on kinematic, dynamic and fp32 contexts, on shapes casc_ric.hip is not built for
+ * and with vc_qp.solver = 2 (the condensed kernel has no detection, and an explicit choice of it is
+ * not rerouted); VC_E_ARG when dyn_mpc.trust_Fx <= 0 (R needs the trust region). */
+int vc_set_casc_infeasibility(vc_ctx* ctx, int on, double eps);
+
+/* The Farkas vectors y[B][12N-3+6M] (fp64, M = casc.horizon_pm) of the last vc_solve* on this
+ * context and, where qp_index is not NULL, qp_index[B]: the 0-based SQP iteration whose QP was
+ * certified infeasible, -1 where none was (y's row is then zero).  Rows in the order of
+ * oracle/casc_sqp.py casc_qp: the single-track stages as in vc_get_sqp_farkas (12N - 3 rows), then
+ * per point-mass stage m [V >= V_min, Fx <= Peng / V, Fx up, Fx dn, Fy up, Fy dn] at 12N - 3 + 6m;
+ * y >= 0, sum y = 1, a multiplier of those rows as casc_qp scales them.  y and qp_index follow the
+ * pointer convention of `flags`.  VC_E_ARG when the detection is off or B exceeds the last solve's
+ * batch. */
+int vc_get_casc_farkas(vc_ctx* ctx, int B, void* y, int32_t* qp_index, int flags);
+
 /* One MPC step for B problems (B <= max_batch):
  *   in:     x0[B][nx], kappa[B][N], ds[B][N], ubar[B][N][nu] (warm start)
  *   out:    ubar <- u*[B][N][nu], xbar <- x*[B][NS][nx], u0[B][nu] = u*[:,0],
@@ -324,7 +361,8 @@ int vc_solve_from(vc_ctx* ctx, int B, const void* x0, const void* kappa, const v
  * 4 every converged QP's answer certified by the active-set polish, 16 the SQP stopped early (a QP after the first had no solution: its step was refused and
  * the earlier iterate returned, so `status` reflects the QPs before it only), 32 a QP was certified
  * infeasible by a Farkas vector (single-track fp64 with vc_set_sqp_infeasibility on: with status
- * VC_INFEASIBLE the first QP, with bit 16 a later one; vc_get_sqp_farkas); [3] the largest
+ * VC_INFEASIBLE the first QP, with bit 16 a later one; vc_get_sqp_farkas; cascaded fp64 with
+ * vc_set_casc_infeasibility on likewise; vc_get_casc_farkas); [3] the largest
  * interior-point iteration count of one QP. */
 int vc_solve_diag(vc_ctx* ctx, int B, const void* x0, const void* kappa, const void* ds,
                   void* xbar, void* ubar, void* u0, int32_t* status, int32_t* iters, void* diag,

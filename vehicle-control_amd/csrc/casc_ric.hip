@@ -26,6 +26,11 @@
 // problems solved by a backward Riccati recursion over the H stages (O(H) per iteration;
 // the condensed kernel pays O(H^3)) and a forward rollout; lane k owns stage k's rows,
 // slacks and multipliers in registers.
+//   infeasible (DET instantiation, vc_set_casc_infeasibility): from the second interior-point
+//              iteration of every QP the normalised multipliers are tested as a Farkas vector of the
+//              linearised rows over all H stages.  A certificate in the first QP ends the problem as
+//              VC_INFEASIBLE at the warm start; in a later one: the existing `stopped` path, only
+//              sooner.  y goes to A.farkas, the QP to A.qp_index.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -277,7 +282,7 @@ __device__ __forceinline__ CrJP<JG> cr_jac(CrSmem<N, M, JG>& s, int b) {
   else return s.J;
 }
 
-template <int N, int M, int TYRE, bool JG>
+template <int N, int M, int TYRE, bool JG, bool DET>
 __global__ __launch_bounds__(WTH) void casc_ric_kernel(CascSqpArgs A) {
   constexpr int H = N + M;
   static_assert(N >= 2 && M >= 2 && H <= WTH, "one lane per stage");
@@ -315,6 +320,7 @@ __global__ __launch_bounds__(WTH) void casc_ric_kernel(CascSqpArgs A) {
   int it_total = 0, it_max = 0;
   bool all_conv = true, any_fail = false, stopped = false;  // stopped: a later QP ended the SQP early
   bool all_pol = true;  // every converged QP's answer certified by the active-set polish
+  bool cert = false;    // DET: a QP was certified infeasible (its Farkas vector is in A.farkas)
   double last_res = 0.0, last_mu = 0.0;
   const double tol_r = 1e-10, tol_mu = 1e-13;
 
@@ -987,9 +993,78 @@ __global__ __launch_bounds__(WTH) void casc_ric_kernel(CascSqpArgs A) {
       for (int e = 0; e < NQ; ++e) s.u.q.Qt[k][e] = Qt[e];
     };
 
+    // Infeasibility test (DET; st_sqp.hip's over the H stages): y = lam / |lam|_1 is a
+    // Farkas vector of the rows C dz <= d when d'y + R |C'y|_inf < 0, R = sum_{k<N} [trust_Fx / S +
+    // max(0, up_k, dn_k)] + sum_{m<M} 2 trust_Fx / S >= |dz|_1 of every feasible dz (rows 8..11 are boxes
+    // on both kinds of stage).  C'y on the 2H inputs is the open-loop adjoint sweep of the rows' stage
+    // vectors sum_i m_i lam_i c_i through J: the single-track RK4 Jacobians, the switching map at
+    // k = N - 1 and the point-mass Euler Jacobians.  It runs only when d'lam < 0, borrows s.u.q.g and
+    // puts the stage gradients grk back (a carried dual residual may still be replaced by a sweep of
+    // them; set_h rewrites g from registers afterwards).  The guard is relative to the magnitude of
+    // the terms the value is summed from, the sweep's costates included (the open-loop sweep
+    // amplifies rounding at low speed, see dual_residual).
+    [[maybe_unused]] auto farkas_test = [&](const double* grk) -> bool {
+      // d'lam, |lam|_1 and sum |d_i| lam_i: summed here for the gate and again after the sweep (nothing
+      // but the sweep's own state is then held across it, where the whole interior point's is live)
+      auto sums = [&](double& dl, double& l1, double& dab) {
+        dl = l1 = dab = 0.0;
+#pragma unroll
+        for (int i = 0; i < NR; ++i) {
+          const double ml = R.m(i) * la[i];
+          dl += ml * R.d[i];
+          l1 += ml;
+          dab += ml * fabs(R.d[i]);
+        }
+        dl = wsum(dl);
+        l1 = wsum(l1);
+        dab = wsum(dab);
+      };
+      {
+        double dl, l1, dab;
+        sums(dl, l1, dab);
+        if (!(dl < 0.0) || !(l1 > 0.0) || !(l1 < 1e300)) return false;  // uniform
+      }
+      if (stl) {
+        double ml[NR], ck[9];
+#pragma unroll
+        for (int i = 0; i < NR; ++i) ml[i] = R.m(i) * la[i];
+#pragma unroll
+        for (int e = 0; e < 9; ++e) ck[e] = 0.0;
+        row_adjoint(R, ml, ck);
+#pragma unroll
+        for (int e = 0; e < 9; ++e) s.u.q.g[k][e] = ck[e];
+      }
+      WSYNC();
+      // each lane's largest costate; lanes 7, 8 (fk) carry the two input components of every stage
+      double rho = 0.0, amax = 0.0;
+      // (one stage's operands at a time: the test is rare, and the lookahead of the other sweeps
+      // would hold a second stage's operands)
+#pragma unroll 1
+      for (int kk = H - 1; kk >= 0; --kk) {
+        BwdOps A4;
+        bwd_load(kk, s.u.q.g, A4);
+        rho = bwd_g(kk, A4, rho);
+        amax = fmax(amax, fabs(rho));
+      }
+      if (stl) {
+#pragma unroll
+        for (int e = 0; e < 9; ++e) s.u.q.g[k][e] = grk[e];
+      }
+      WSYNC();
+      const double cmax = wmax(fk ? amax : 0.0);  // |C'y|_inf |lam|_1 over the 2H inputs
+      amax = wmax(amax);
+      double dl, l1, dab;
+      sums(dl, l1, dab);
+      // (point-mass stages: rows 8, 9 are the Fy trust region, so the same expression gives 2 trust_Fx / S)
+      const double rb = wsum(stl ? (R.m(10) > 0.0 ? R.d[10] : 1e300) + fmax(0.0, fmax(R.d[8], R.d[9])) : 0.0);
+      // (d'y + R |C'y|_inf < -eps (1 + magnitude), times |lam|_1; a NaN anywhere compares false)
+      return dl + rb * cmax < -kargs<CascSqpArgs>()->detect_eps * (l1 + dab + rb * amax);
+    };
+
     // ---------------- interior point (Mehrotra predictor-corrector) ----------------
     int it = 0;
     bool conv = false, fail = false;
+    bool infeas = false;  // DET: this QP's rows are certified infeasible
     // dual residual carried by the steps: the LQ direction solves the linearised
     // stationarity exactly, so a step of length alpha scales the condensed gradient by
     // (1 - alpha); the adjoint sweep runs at the first iteration and wherever the carried value
@@ -1034,6 +1109,11 @@ __global__ __launch_bounds__(WTH) void casc_ric_kernel(CascSqpArgs A) {
       bool rd_cl = carried || kvalid;
       last_res = fmax(rdm, rpm);
       last_mu = mu;
+      if constexpr (DET) {
+        // ahead of the three exits through `fail` below (non-finite residuals, factorisation
+        // breakdown: none of them changes the multipliers), so a diverging QP is still labelled
+        if (it >= 1 && farkas_test(grk)) { infeas = true; break; }
+      }
       if (!(last_res == last_res) || !(mu == mu) || last_res > 1e300) { fail = true; break; }
       if (have_rd && mu <= 1e2 * tol_mu && fmax(rdm, rpm) <= 1e3 * rtol) {
         // the carried value would end the loop here or below: take the sweep's
@@ -1124,6 +1204,39 @@ __global__ __launch_bounds__(WTH) void casc_ric_kernel(CascSqpArgs A) {
     }
     it_total += it;
     it_max = max(it_max, it);
+    if constexpr (DET) {
+      // the certificate y = lam / |lam|_1 goes out in the oracle's row order (casc_qp): single-track
+      // stage k its present rows in slot order, point-mass stage m (V >= V_min, Fx <= Peng / V, Fx up,
+      // Fx dn, Fy up, Fy dn) = slots (0, 3, 10, 11, 8, 9)
+      if (infeas) {
+        double l1 = 0.0;
+#pragma unroll
+        for (int i = 0; i < NR; ++i) l1 += R.m(i) * la[i];
+        l1 = wsum(l1);
+        if (stl) {
+          constexpr int MW = 12 * N - 3 + 6 * M;
+          double* fkv = kargs<CascSqpArgs>()->farkas + (size_t)b * MW;
+          if (pm) {
+            fkv += 12 * N - 3 + 6 * (k - N);
+            constexpr int slot[6] = {0, 3, 10, 11, 8, 9};
+#pragma unroll
+            for (int i = 0; i < 6; ++i) fkv[i] = R.m(slot[i]) * la[slot[i]] / l1;
+          } else {
+            fkv += k >= 1 ? 12 * k - 3 : 0;
+#pragma unroll
+            for (int i = 0; i < NR; ++i) {
+              if (i >= 3) fkv[k >= 1 ? i : i - 3] = R.m(i) * la[i] / l1;
+              else if (k >= 1) fkv[i] = R.m(i) * la[i] / l1;
+            }
+          }
+        }
+        if (l == 0) kargs<CascSqpArgs>()->qp_index[b] = sq;
+        cert = true;
+        // the first QP: the problem ends here, at the warm start and its rollout (s.ub, s.xs);
+        // a later one takes the stopped path below
+        if (sq == 0) break;
+      }
+    }
 
     // ---------------- active-set polish (round 5; st_sqp.hip has the same) ----------------
     // The interior point's iterate is only as close to the QP's optimum as its weakly active rows
@@ -1282,10 +1395,18 @@ __global__ __launch_bounds__(WTH) void casc_ric_kernel(CascSqpArgs A) {
     A.x_out[(size_t)b * 8 * H + e] = v;
   }
   finite = __all(finite ? 1 : 0) != 0;
+  if constexpr (DET) {
+    if (!cert) {  // uniform: no certificate, a zero row and -1
+      constexpr int MW = 12 * N - 3 + 6 * M;
+      for (int e = l; e < MW; e += WTH) A.farkas[(size_t)b * MW + e] = 0.0;
+      if (l == 0) A.qp_index[b] = -1;
+    }
+  }
   if (l < 2) A.u0[(size_t)b * 2 + l] = s.ub[0][l];
   if (l == 0) {
     int32_t st;
     if (!finite || s.flag[0] == VC_NONFINITE) st = VC_NONFINITE;
+    else if (DET && cert && !stopped) st = VC_INFEASIBLE;  // the first QP has no feasible point
     else if (s.flag[2] == 0) st = VC_OUT_OF_DOMAIN;  // x* (the last rollout) outside the models' domain
     else if (all_conv) st = VC_SOLVED;
     else st = VC_MAX_ITER;
@@ -1296,7 +1417,8 @@ __global__ __launch_bounds__(WTH) void casc_ric_kernel(CascSqpArgs A) {
       A.diag[(size_t)b * DS + 0] = last_res;
       A.diag[(size_t)b * DS + 1] = last_mu;
       A.diag[(size_t)b * DS + 2] =
-          double((any_fail ? 1 : 0) | (all_conv ? 2 : 0) | (all_pol ? 4 : 0) | (stopped ? 16 : 0));
+          double((any_fail ? 1 : 0) | (all_conv ? 2 : 0) | (all_pol ? 4 : 0) | (stopped ? 16 : 0) |
+                 (DET && cert ? 32 : 0));
       A.diag[(size_t)b * DS + 3] = double(it_max);
     }
   }
@@ -1338,16 +1460,19 @@ template <int N, int M, int TYRE>
 void cr_launch(const CascSqpArgs& a, hipStream_t stream) {
   if constexpr (cr_j_global_ok<N, M>()) {
     if (cr_jg_pick<N, M>(a.B)) {
-      hipLaunchKernelGGL((casc_ric_kernel<N, M, TYRE, true>), dim3(a.B), dim3(WTH), 0, stream, a);
+      if (a.detect) hipLaunchKernelGGL((casc_ric_kernel<N, M, TYRE, true, true>), dim3(a.B), dim3(WTH), 0, stream, a);
+      else hipLaunchKernelGGL((casc_ric_kernel<N, M, TYRE, true, false>), dim3(a.B), dim3(WTH), 0, stream, a);
       return;
     }
   }
-  hipLaunchKernelGGL((casc_ric_kernel<N, M, TYRE, false>), dim3(a.B), dim3(WTH), 0, stream, a);
+  if (a.detect) hipLaunchKernelGGL((casc_ric_kernel<N, M, TYRE, false, true>), dim3(a.B), dim3(WTH), 0, stream, a);
+  else hipLaunchKernelGGL((casc_ric_kernel<N, M, TYRE, false, false>), dim3(a.B), dim3(WTH), 0, stream, a);
 }
 
 hipError_t launch_casc_ric(const CascSqpArgs& a, int N, int M, hipStream_t stream) {
   if (a.B <= 0) return hipSuccess;
   if (casc_ric_jws_doubles(N, M, a.B) && !a.jws) return hipErrorInvalidValue;  // the workspace the kernel needs
+  if (a.detect && (!a.farkas || !a.qp_index)) return hipErrorInvalidValue;
   const bool lin = a.car.tyre == VC_TYRE_LINEAR;
 #define VC_CASE(n, m)                                \
   if (N == n && M == m) {                           \

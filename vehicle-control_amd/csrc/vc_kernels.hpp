@@ -297,6 +297,12 @@ struct CascSqpArgs {
   vc_casc_mpc cw;
   vc_qp qp;
   vc_obstacles obs;
+  // infeasibility detection (vc_set_casc_infeasibility; casc_ric.hip only, casc_sqp.hip does not read
+  // them), appended so that the offsets the kernels read without it stay where they were
+  int detect;           // 1: launch the DET instantiation (the Farkas test runs inside each interior point)
+  double detect_eps;    // roundoff guard of the test
+  double* farkas;       // [B][12N-3+6M] certificate y in the row order of oracle/casc_sqp.py casc_qp
+  int32_t* qp_index;    // [B] SQP iteration whose QP was certified, -1: none
 };
 
 // Elementwise model kernels (models.hip).

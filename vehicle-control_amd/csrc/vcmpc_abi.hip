@@ -44,6 +44,12 @@ struct vc_ctx {
   void* sqp_farkas = nullptr;    // [max_batch][12N-3] fp64, allocated on first enable
   void* sqp_qp_index = nullptr;  // [max_batch] int32
   int sqp_farkas_B = 0;
+  // vc_set_casc_infeasibility: the same for the stagewise cascaded SQP (casc_ric.hip)
+  bool casc_detect = false;
+  double casc_detect_eps = 1e-9;
+  void* casc_farkas = nullptr;    // [max_batch][12N-3+6M] fp64, allocated on first enable
+  void* casc_qp_index = nullptr;  // [max_batch] int32
+  int casc_farkas_B = 0;
   std::string err;
 };
 
@@ -256,6 +262,13 @@ int casc_solve(vc_ctx* c, int B, const void* x0, const void* kappa, const void* 
     if (const size_t jd = vc::casc_ric_jws_doubles(c->N, c->p.casc.horizon_pm, B)) {
       if (int r = ensure_scratch(c, &c->jw, &c->jw_bytes, (size_t)B * jd * 8)) return r;
       a.jws = (double*)c->jw;
+    }
+    if (c->casc_detect) {
+      a.detect = 1;
+      a.detect_eps = c->casc_detect_eps;
+      a.farkas = (double*)c->casc_farkas;
+      a.qp_index = (int32_t*)c->casc_qp_index;
+      c->casc_farkas_B = B;
     }
     VC_HIP(c, vc::launch_casc_ric(a, c->N, c->p.casc.horizon_pm, c->stream));
   }
@@ -473,6 +486,8 @@ void vc_destroy(vc_ctx* c) {
   if (c->farkas) (void)hipFree(c->farkas);
   if (c->sqp_farkas) (void)hipFree(c->sqp_farkas);
   if (c->sqp_qp_index) (void)hipFree(c->sqp_qp_index);
+  if (c->casc_farkas) (void)hipFree(c->casc_farkas);
+  if (c->casc_qp_index) (void)hipFree(c->casc_qp_index);
   if (c->own) (void)hipStreamDestroy(c->own);
   delete c;
 }
@@ -576,6 +591,48 @@ int vc_get_sqp_farkas(vc_ctx* c, int B, void* y, int32_t* qp_index, int flags) {
   const hipMemcpyKind kind = flags == VC_DEVICE_PTRS ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
   VC_HIP(c, hipMemcpyAsync(y, c->sqp_farkas, (size_t)B * (12 * c->N - 3) * 8, kind, c->stream));
   if (qp_index) VC_HIP(c, hipMemcpyAsync(qp_index, c->sqp_qp_index, (size_t)B * 4, kind, c->stream));
+  if (flags != VC_DEVICE_PTRS) VC_HIP(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// rows of a cascaded QP in oracle/casc_sqp.py casc_qp's order: 12N - 3 single-track, 6 per point-mass stage
+static size_t casc_rows(const vc_ctx* c) { return (size_t)(12 * c->N - 3 + 6 * c->p.casc.horizon_pm); }
+
+int vc_set_casc_infeasibility(vc_ctx* c, int on, double eps) {
+  if (!c) return VC_E_ARG;
+  if (c->model != VC_MODEL_CASCADED || c->dtype != VC_F64 || !vc::casc_ric_built(c->N, c->p.casc.horizon_pm))
+    return fail(c, VC_E_UNSUPPORTED,
+                "vc_set_casc_infeasibility: the stagewise cascaded fp64 SQP kernel only (cascaded fp64, N=20, "
+                "horizon_pm=15/25/35/40); model=%d dtype=%d N=%d horizon_pm=%d", c->model, c->dtype, c->N,
+                c->p.casc.horizon_pm);
+  if (c->p.qp.solver == 2)
+    return fail(c, VC_E_UNSUPPORTED,
+                "vc_set_casc_infeasibility: qp.solver=2 asks for the condensed kernel, which has no detection");
+  if (!(c->p.dyn_mpc.trust_Fx > 0))
+    return fail(c, VC_E_ARG, "vc_set_casc_infeasibility: dyn_mpc.trust_Fx must be > 0 (it bounds |dz|_1)");
+  if (on && !c->casc_farkas) {
+    VC_HIP(c, hipSetDevice(c->device));
+    const size_t nb = (size_t)(c->max_batch > 0 ? c->max_batch : 1);
+    VC_HIP(c, hipMalloc(&c->casc_farkas, nb * casc_rows(c) * 8));
+    VC_HIP(c, hipMalloc(&c->casc_qp_index, nb * 4));
+  }
+  c->casc_detect = on != 0;
+  c->casc_detect_eps = eps > 0.0 ? eps : 1e-9;
+  c->casc_farkas_B = 0;  // no solve has written certificates under this setting yet
+  return 0;
+}
+
+int vc_get_casc_farkas(vc_ctx* c, int B, void* y, int32_t* qp_index, int flags) {
+  if (int r = check_common(c, B, flags)) return r;
+  if (!c->casc_detect || !c->casc_farkas || !c->casc_qp_index)
+    return fail(c, VC_E_ARG, "vc_get_casc_farkas: infeasibility detection is off");
+  if (B > c->casc_farkas_B)
+    return fail(c, VC_E_ARG, "vc_get_casc_farkas: B=%d exceeds the last solve's %d", B, c->casc_farkas_B);
+  if (!y) return fail(c, VC_E_ARG, "null pointer");
+  if (B == 0) return 0;
+  const hipMemcpyKind kind = flags == VC_DEVICE_PTRS ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  VC_HIP(c, hipMemcpyAsync(y, c->casc_farkas, (size_t)B * casc_rows(c) * 8, kind, c->stream));
+  if (qp_index) VC_HIP(c, hipMemcpyAsync(qp_index, c->casc_qp_index, (size_t)B * 4, kind, c->stream));
   if (flags != VC_DEVICE_PTRS) VC_HIP(c, hipStreamSynchronize(c->stream));
   return 0;
 }

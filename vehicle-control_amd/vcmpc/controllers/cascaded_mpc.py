@@ -185,12 +185,16 @@ class BatchedCascadedMPC(Controller):
         self.ds_pm = float(config["ds_pm"])
         self.ns, self.na = len(car.state), len(car.input)
         self.B = int(batch)
+        # qp.detect_infeasible (default false): as in BatchedSingleTrackMPC, over the N + M stages
+        # (vc_set_casc_infeasibility); the neutral retry below handles status 4 like any other != 0
+        self.detect_infeasible = bool((config.get("qp") or {}).get("detect_infeasible", False))
         self.ctx = Context(model=_abi.VC_MODEL_CASCADED, N=self.N, max_batch=self.B, dtype=_abi.VC_F64,
                            device=device,
                            params=make_params(dyn_car=car.config, dyn_mpc=dict(config, qp=dyn_qp_block(config)),
                                               tyre=getattr(car, "tyre", "fiala"),
                                               obstacles=obstacle_list(car, config),
-                                              obstacle_inside=bool(config.get("obstacle_inside", False))))
+                                              obstacle_inside=bool(config.get("obstacle_inside", False))),
+                           detect_infeasible=self.detect_infeasible)
         # warm starts: cascaded_mpc.py:72-76 (ones over H columns, Ux + 3 on the single-track part)
         rng = np.random.RandomState(seed) if seed is not None else np.random
         self.state_prediction = np.ones((self.B, self.ns, self.H))
@@ -199,6 +203,8 @@ class BatchedCascadedMPC(Controller):
         self.status = np.zeros(self.B, np.int32)
         self.iters = np.zeros(self.B, np.int32)
         self._fresh = np.ones(self.B, bool)  # no solution yet: the tail gets the neutral guess
+        # per vehicle: control steps whose first solve was certified infeasible (qp.detect_infeasible)
+        self.infeasible_steps = np.zeros(self.B, np.int64)
 
     def _neutral(self, x0, kappa):
         """Neutral warm start [B, H, 2]: single track Fx = w = 0; point mass Fx = the drag at
@@ -231,6 +237,7 @@ class BatchedCascadedMPC(Controller):
         np.clip(ubar[:, :self.N, IW], ic["w_min"], ic["w_max"], out=ubar[:, :self.N, IW])
         u0, xbar, ustar, status, iters = self.ctx.solve(x0, kappa, ds, ubar)
         bad = status != 0
+        self.infeasible_steps += status == _abi.VC_INFEASIBLE
         if bad.any():
             idx = np.nonzero(bad)[0]
             ux_n = np.repeat(x0[idx, IUX, None], self.H, axis=1)   # neutral horizon (see BatchedSingleTrackMPC)

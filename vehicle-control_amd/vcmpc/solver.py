@@ -56,6 +56,9 @@ class Context:
                 # the single-track fp64 SQP has its own entry point (vc_set_sqp_infeasibility)
                 if model == _abi.VC_MODEL_DYNAMIC and dtype == _abi.VC_F64:
                     self.set_sqp_infeasibility(True, infeasible_eps)
+                # ... and so has the cascaded fp64 SQP (vc_set_casc_infeasibility)
+                elif model == _abi.VC_MODEL_CASCADED and dtype == _abi.VC_F64:
+                    self.set_casc_infeasibility(True, infeasible_eps)
                 else:
                     self.set_infeasibility(True, infeasible_eps)
             except Exception:
@@ -153,6 +156,39 @@ class Context:
             qi = np.empty((B,), np.int32)
             ptrs, flags = (C.c_void_p(y.ctypes.data), C.c_void_p(qi.ctypes.data)), _abi.VC_HOST_PTRS
         self._check(self.lib.vc_get_sqp_farkas(self._h, B, ptrs[0], ptrs[1], flags))
+        return y, qi
+
+    def set_casc_infeasibility(self, on: bool, eps: float = 0.0):
+        """``vc_set_casc_infeasibility``: in-kernel infeasibility detection of the stagewise cascaded
+        fp64 SQP (csrc/casc_ric.hip).  On: a problem whose first QP has no feasible point ends with
+        status ``VC_INFEASIBLE`` (4); a later infeasible QP ends the SQP at the current iterate as
+        before, only sooner.  Either way ``casc_farkas()`` returns the proof.  ``eps <= 0`` keeps the
+        default guard 1e-9.  Raises ``VcError``: VC_E_UNSUPPORTED on kinematic / dynamic / fp32
+        contexts, on tails the stagewise kernel is not built for and with ``qp.solver = 2``;
+        VC_E_ARG when ``trust_Fx <= 0``."""
+        self._check(self.lib.vc_set_casc_infeasibility(self._h, int(bool(on)), float(eps)))
+        self.detect_infeasible = bool(on)
+        self._last = None
+
+    def casc_farkas(self, B: int | None = None):
+        """``vc_get_casc_farkas``: ``(y[B, 12N - 3 + 6M], qp_index[B])`` of the last solve -- rows in
+        the order of oracle/casc_sqp.py ``casc_qp`` (M = horizon_pm), ``qp_index`` the SQP iteration
+        whose QP was certified infeasible or -1 (``y``'s row is then zero).  Numpy arrays after a
+        host-array solve, torch tensors on the context's device after a device-tensor one.  Raises
+        ``VcError`` when the detection is off."""
+        last_B, dev = self._last if self._last is not None else (0, None)
+        B = last_B if B is None else int(B)
+        m = 12 * self.N - 3 + 6 * (self.NH - self.N)
+        if dev is not None:
+            import torch
+            y = torch.empty((B, m), dtype=torch.float64, device=dev)
+            qi = torch.empty((B,), dtype=torch.int32, device=dev)
+            ptrs, flags = (C.c_void_p(y.data_ptr()), C.c_void_p(qi.data_ptr())), _abi.VC_DEVICE_PTRS
+        else:
+            y = np.empty((B, m), np.float64)
+            qi = np.empty((B,), np.int32)
+            ptrs, flags = (C.c_void_p(y.ctypes.data), C.c_void_p(qi.ctypes.data)), _abi.VC_HOST_PTRS
+        self._check(self.lib.vc_get_casc_farkas(self._h, B, ptrs[0], ptrs[1], flags))
         return y, qi
 
     def synchronize(self):
