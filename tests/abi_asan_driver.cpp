@@ -34,7 +34,14 @@ int main() {
   CHECK(vc_create(0, VC_MODEL_DYNAMIC, 40, 64, VC_F64, &p) == nullptr);
   p.obs.inside = 0;
   vc_destroy(nullptr);
-  vc_ctx* c = vc_create(0, VC_MODEL_KINEMATIC, 20, 64, VC_F64, &p);
+  // a null context is an argument error in all six infeasibility entry points
+  CHECK(vc_set_infeasibility(nullptr, 1, 0.0) == VC_E_ARG);
+  CHECK(vc_set_sqp_infeasibility(nullptr, 1, 0.0) == VC_E_ARG);
+  CHECK(vc_set_casc_infeasibility(nullptr, 1, 0.0) == VC_E_ARG);
+  CHECK(vc_get_farkas(nullptr, 0, nullptr, VC_HOST_PTRS) == VC_E_ARG);
+  CHECK(vc_get_sqp_farkas(nullptr, 0, nullptr, nullptr, VC_HOST_PTRS) == VC_E_ARG);
+  CHECK(vc_get_casc_farkas(nullptr, 0, nullptr, nullptr, VC_DEVICE_PTRS) == VC_E_ARG);
+  vc_ctx* c =vc_create(0, VC_MODEL_KINEMATIC, 20, 64, VC_F64, &p);
   if (!c) {
     std::printf("no device: %s\n", vc_last_error(nullptr));
   } else {

@@ -16,6 +16,17 @@
 #include "vcmpc.h"
 
 
+// In-kernel infeasibility detection (vc_set_infeasibility / vc_set_sqp_infeasibility /
+// vc_set_casc_infeasibility) and the Farkas certificates of the last solve.
+struct Detect {
+  bool on = false;
+  double eps = 1e-9;
+  void* farkas = nullptr;    // [max_batch][rows] fp64, allocated on first enable, kept when turned off
+  void* qp_index = nullptr;  // [max_batch] int32, the SQP models only
+  size_t rows = 0;           // per problem: 7N-3 (kinematic), 12N-3 (single track), 12N-3+6M (cascaded)
+  int B = 0;                 // batch of the last solve that wrote them
+};
+
 struct vc_ctx {
   int device = 0, model = 0, N = 0, max_batch = 0, dtype = 0;
   vc_params p{};
@@ -33,23 +44,7 @@ struct vc_ctx {
   void* jw = nullptr;     // single-track / cascaded SQP: stage Jacobians of the kernels that keep them out of LDS
   size_t jw_bytes = 0;
   int fault_iter = -1, fault_problem = -1;  // vc_debug_qp_fault (tests only)
-  // vc_set_infeasibility: the Farkas test of the stagewise kinematic kernel and its certificates
-  bool detect = false;
-  double detect_eps = 1e-9;
-  void* farkas = nullptr;  // [max_batch][7N-3] fp64, allocated on first enable
-  int farkas_B = 0;        // batch of the last solve that wrote it
-  // vc_set_sqp_infeasibility: the same for the single-track SQP (st_sqp.hip)
-  bool sqp_detect = false;
-  double sqp_detect_eps = 1e-9;
-  void* sqp_farkas = nullptr;    // [max_batch][12N-3] fp64, allocated on first enable
-  void* sqp_qp_index = nullptr;  // [max_batch] int32
-  int sqp_farkas_B = 0;
-  // vc_set_casc_infeasibility: the same for the stagewise cascaded SQP (casc_ric.hip)
-  bool casc_detect = false;
-  double casc_detect_eps = 1e-9;
-  void* casc_farkas = nullptr;    // [max_batch][12N-3+6M] fp64, allocated on first enable
-  void* casc_qp_index = nullptr;  // [max_batch] int32
-  int casc_farkas_B = 0;
+  Detect det;             // vc_set_*_infeasibility (a context has one model, so one state)
   std::string err;
 };
 
@@ -99,33 +94,75 @@ int ensure_arena(vc_ctx* c, size_t bytes) {
   return 0;
 }
 
-// Staging plan for a host-pointer call: each buffer gets an aligned arena slice.
-struct Slot {
-  const void* host_in;  // copied H2D before the launch (may be null)
-  void* host_out;       // copied D2H after the launch (may be null)
-  size_t bytes;
-  void* dev;
+size_t al256(size_t b) { return (b + 255) & ~size_t(255); }
+
+// A device pointer of whatever element type and constness the kernel's argument wants.
+struct Ptr {
+  void* p = nullptr;
+  template <class T> operator T*() const { return static_cast<T*>(p); }
 };
 
-int stage(vc_ctx* c, std::vector<Slot>& slots) {
-  size_t total = 0;
-  for (auto& s : slots) total += (s.bytes + 255) & ~size_t(255);
-  if (int r = ensure_arena(c, total ? total : 256)) return r;
-  size_t off = 0;
-  for (auto& s : slots) {
-    s.dev = static_cast<char*>(c->arena) + off;
-    off += (s.bytes + 255) & ~size_t(255);
-    if (s.host_in && s.bytes) VC_HIP(c, hipMemcpyAsync(s.dev, s.host_in, s.bytes, hipMemcpyHostToDevice, c->stream));
-  }
-  return 0;
-}
+// The buffers of one entry-point call.  Each is declared once, inside the callable given to bind(),
+// and the declaration returns the pointer for the kernel: the caller's own under VC_DEVICE_PTRS
+// (no copy, no synchronise), a 256-byte-aligned arena slice under VC_HOST_PTRS.  There bind() runs
+// the declarations twice: first to add the sizes up, so the arena grows at most once and before any
+// copy, then to hand out the slices and issue the H2D copies in declaration order.  After the
+// launches finish() issues the D2H copies and synchronises once.  An optional buffer passed as NULL
+// takes no bytes and reaches the kernel as nullptr in both modes.
+class Staging {
+ public:
+  Staging(vc_ctx* c, int flags) : c_(c), host_(flags == VC_HOST_PTRS) {}
 
-int unstage(vc_ctx* c, const std::vector<Slot>& slots) {
-  for (auto& s : slots)
-    if (s.host_out && s.bytes) VC_HIP(c, hipMemcpyAsync(s.host_out, s.dev, s.bytes, hipMemcpyDeviceToHost, c->stream));
-  VC_HIP(c, hipStreamSynchronize(c->stream));
-  return 0;
-}
+  struct Pair {
+    Ptr rd, wr;  // what the kernel reads / writes; null where src / dst is
+  };
+  // one slice copied in from src (if any) and back out to dst (if any)
+  Pair pair(const void* src, void* dst, size_t bytes) {
+    if (!host_) return {{const_cast<void*>(src)}, {dst}};
+    if (!src && !dst) return {};
+    const size_t at = off_;
+    off_ += al256(bytes);
+    if (!placing_) return {};
+    void* dev = static_cast<char*>(c_->arena) + at;
+    if (src && bytes && err_ == hipSuccess) err_ = hipMemcpyAsync(dev, src, bytes, hipMemcpyHostToDevice, c_->stream);
+    if (dst && bytes) outs_.push_back({dst, dev, bytes});
+    return {{src ? dev : nullptr}, {dst ? dev : nullptr}};
+  }
+  Ptr in(const void* host, size_t bytes) { return pair(host, nullptr, bytes).rd; }
+  Ptr out(void* host, size_t bytes) { return pair(nullptr, host, bytes).wr; }
+  Ptr inout(void* host, size_t bytes) { return pair(host, host, bytes).wr; }
+
+  template <class F>
+  int bind(F&& declare) {
+    declare();
+    if (!host_) return 0;
+    if (int r = ensure_arena(c_, off_ ? off_ : 256)) return r;
+    off_ = 0;
+    placing_ = true;
+    declare();
+    if (err_ != hipSuccess) return fail(c_, VC_E_HIP, "hipMemcpyAsync (H2D): %s", hipGetErrorString(err_));
+    return 0;
+  }
+
+  int finish() {
+    if (!host_) return 0;
+    for (const Out& o : outs_) VC_HIP(c_, hipMemcpyAsync(o.host, o.dev, o.bytes, hipMemcpyDeviceToHost, c_->stream));
+    VC_HIP(c_, hipStreamSynchronize(c_->stream));
+    return 0;
+  }
+
+ private:
+  struct Out {
+    void* host;
+    const void* dev;
+    size_t bytes;
+  };
+  vc_ctx* c_;
+  bool host_, placing_ = false;
+  size_t off_ = 0;
+  hipError_t err_ = hipSuccess;
+  std::vector<Out> outs_;
+};
 
 int check_common(vc_ctx* c, int B, int flags) {
   if (!c) return VC_E_ARG;
@@ -153,7 +190,6 @@ vc::ModelArgs model_args(const vc_ctx* c, int B) {
 // cascaded context); xbar has N + 1 (kinematic) or H state columns
 int nh_of(const vc_ctx* c) { return c->N + (c->model == VC_MODEL_CASCADED ? c->p.casc.horizon_pm : 0); }
 int ns_of(const vc_ctx* c) { return c->model == VC_MODEL_KINEMATIC ? c->N + 1 : nh_of(c); }
-size_t al256(size_t b) { return (b + 255) & ~size_t(255); }
 vc::TrackTable track_table(const vc_ctx* c) {
   return vc::TrackTable{static_cast<const double*>(c->track), c->track_n, c->track_h, c->track_len};
 }
@@ -170,7 +206,7 @@ bool kin_condensed_cfg(const vc_ctx* c) {
 }
 // ... and so is the infeasibility detection (vc_set_infeasibility): the solve of a context that has it
 // on goes to the stagewise kernel; vc_condense keeps the condensed kernel's H, g either way
-bool kin_condensed(const vc_ctx* c) { return kin_condensed_cfg(c) && !c->detect; }
+bool kin_condensed(const vc_ctx* c) { return kin_condensed_cfg(c) && !c->det.on; }
 bool kin_solve_built(const vc_ctx* c) {
   return c->model == VC_MODEL_KINEMATIC && c->dtype == VC_F64 && (kin_condensed(c) || vc::kin_ric_built(c->N));
 }
@@ -187,6 +223,55 @@ bool casc_stagewise(const vc_ctx* c) {
 bool casc_solve_built(const vc_ctx* c) {
   return c->model == VC_MODEL_CASCADED && c->dtype == VC_F64 &&
          (casc_stagewise(c) || vc::casc_sqp_built(c->N, c->p.casc.horizon_pm));
+}
+
+// vc_set_*_infeasibility behind its entry point's own "supported here" checks: the certificate
+// buffers are sized by max_batch on first enable and kept until vc_destroy.
+int set_detection(vc_ctx* c, int on, double eps, size_t rows, bool with_index) {
+  Detect& d = c->det;
+  if (on && !d.farkas) {
+    VC_HIP(c, hipSetDevice(c->device));
+    const size_t nb = (size_t)(c->max_batch > 0 ? c->max_batch : 1);
+    VC_HIP(c, hipMalloc(&d.farkas, nb * rows * 8));
+    if (with_index) VC_HIP(c, hipMalloc(&d.qp_index, nb * 4));
+  }
+  d.on = on != 0;
+  d.eps = eps > 0.0 ? eps : 1e-9;
+  d.rows = rows;
+  d.B = 0;  // no solve has written certificates under this setting yet
+  return 0;
+}
+
+// vc_get_*_farkas of the entry point `who`, which serves contexts of `model`: on any other context
+// its detection is off by definition.
+int get_detection(vc_ctx* c, const char* who, int model, int B, void* y, int32_t* qp_index, bool with_index,
+                  int flags) {
+  if (int r = check_common(c, B, flags)) return r;
+  const Detect& d = c->det;
+  if (c->model != model || !d.on || !d.farkas || (with_index && !d.qp_index))
+    return fail(c, VC_E_ARG, "%s: infeasibility detection is off", who);
+  if (model == VC_MODEL_KINEMATIC && c->p.qp.kin_sqp > 0)
+    return fail(c, VC_E_UNSUPPORTED, "%s: kin_sqp > 0 solves several QPs per call", who);
+  if (B > d.B) return fail(c, VC_E_ARG, "%s: B=%d exceeds the last solve's %d", who, B, d.B);
+  if (!y) return fail(c, VC_E_ARG, "null pointer");
+  if (B == 0) return 0;
+  const hipMemcpyKind kind = flags == VC_DEVICE_PTRS ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  VC_HIP(c, hipMemcpyAsync(y, d.farkas, (size_t)B * d.rows * 8, kind, c->stream));
+  if (qp_index) VC_HIP(c, hipMemcpyAsync(qp_index, d.qp_index, (size_t)B * 4, kind, c->stream));
+  if (flags != VC_DEVICE_PTRS) VC_HIP(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// The detect / detect_eps / farkas tail of a solve kernel's arguments; true when the detection is on
+// (the SQP kernels then take qp_index too).
+template <class Args>
+bool arm_detection(vc_ctx* c, Args& a, int B) {
+  if (!c->det.on) return false;
+  a.detect = 1;
+  a.detect_eps = c->det.eps;
+  a.farkas = (double*)c->det.farkas;
+  c->det.B = B;
+  return true;
 }
 
 // Cascaded single-track + point-mass SQP (casc_sqp.hip), fp64: arrays span H = N + M stages.
@@ -208,73 +293,37 @@ int casc_solve(vc_ctx* c, int B, const void* x0, const void* kappa, const void* 
   a.cw = c->p.casc;
   a.qp = c->p.qp;
   a.obs = c->p.obs;
-  std::vector<Slot> slots;
-  if (flags == VC_HOST_PTRS) {
-    if (mode == 0) {
-      slots = {{x0, nullptr, (size_t)B * nx * 8, nullptr},
-               {kappa, nullptr, (size_t)B * Hs * 8, nullptr},
-               {ds, nullptr, (size_t)B * Hs * 8, nullptr},
-               {ubar, ubar, (size_t)B * Hs * nu * 8, nullptr},
-               {nullptr, xbar, (size_t)B * Hs * nx * 8, nullptr},
-               {nullptr, u0, (size_t)B * nu * 8, nullptr},
-               {nullptr, status, (size_t)B * 4, nullptr},
-               {nullptr, iters, (size_t)B * 4, nullptr},
-               {nullptr, diag, diag ? (size_t)B * VC_CASC_DIAG_COLS * 8 : 0, nullptr}};
-    } else {
-      slots = {{x0, nullptr, (size_t)B * nx * 8, nullptr},
-               {kappa, nullptr, (size_t)B * Hs * 8, nullptr},
-               {ds, nullptr, (size_t)B * Hs * 8, nullptr},
-               {ubar, nullptr, (size_t)B * Hs * nu * 8, nullptr},
-               {nullptr, H_out, (size_t)B * n * n * 8, nullptr},
-               {nullptr, g_out, (size_t)B * n * 8, nullptr}};
-    }
-    if (int r = stage(c, slots)) return r;
-    a.x0 = (const double*)slots[0].dev;
-    a.kappa = (const double*)slots[1].dev;
-    a.ds = (const double*)slots[2].dev;
-    a.ubar = (const double*)slots[3].dev;
-    if (mode == 0) {
-      a.u_out = (double*)slots[3].dev;
-      a.x_out = (double*)slots[4].dev;
-      a.u0 = (double*)slots[5].dev;
-      a.status = (int32_t*)slots[6].dev;
-      a.iters = (int32_t*)slots[7].dev;
-      a.diag = diag ? (double*)slots[8].dev : nullptr;
-    } else {
-      a.H_out = (double*)slots[4].dev;
-      a.g_out = (double*)slots[5].dev;
-    }
-  } else {
-    a.x0 = (const double*)x0;
-    a.kappa = (const double*)kappa;
-    a.ds = (const double*)ds;
-    a.ubar = (const double*)ubar;
-    a.u_out = (double*)ubar;
-    a.x_out = (double*)xbar;
-    a.u0 = (double*)u0;
-    a.status = status;
-    a.iters = iters;
-    a.diag = (double*)diag;
-    a.H_out = (double*)H_out;
-    a.g_out = (double*)g_out;
-  }
+  Staging st(c, flags);
+  if (int r = st.bind([&] {
+        a.x0 = st.in(x0, (size_t)B * nx * 8);
+        a.kappa = st.in(kappa, (size_t)B * Hs * 8);
+        a.ds = st.in(ds, (size_t)B * Hs * 8);
+        // mode 1 reads the warm start only: ubar is not written back
+        const Staging::Pair u = st.pair(ubar, mode == 0 ? ubar : nullptr, (size_t)B * Hs * nu * 8);
+        a.ubar = u.rd;
+        a.u_out = u.wr;
+        if (mode == 0) {
+          a.x_out = st.out(xbar, (size_t)B * Hs * nx * 8);
+          a.u0 = st.out(u0, (size_t)B * nu * 8);
+          a.status = st.out(status, (size_t)B * 4);
+          a.iters = st.out(iters, (size_t)B * 4);
+          a.diag = st.out(diag, (size_t)B * VC_CASC_DIAG_COLS * 8);
+        } else {
+          a.H_out = st.out(H_out, (size_t)B * n * n * 8);
+          a.g_out = st.out(g_out, (size_t)B * n * 8);
+        }
+      }))
+    return r;
   if (mode == 0 && casc_stagewise(c)) {
     if (const size_t jd = vc::casc_ric_jws_doubles(c->N, c->p.casc.horizon_pm, B)) {
       if (int r = ensure_scratch(c, &c->jw, &c->jw_bytes, (size_t)B * jd * 8)) return r;
       a.jws = (double*)c->jw;
     }
-    if (c->casc_detect) {
-      a.detect = 1;
-      a.detect_eps = c->casc_detect_eps;
-      a.farkas = (double*)c->casc_farkas;
-      a.qp_index = (int32_t*)c->casc_qp_index;
-      c->casc_farkas_B = B;
-    }
+    if (arm_detection(c, a, B)) a.qp_index = (int32_t*)c->det.qp_index;
     VC_HIP(c, vc::launch_casc_ric(a, c->N, c->p.casc.horizon_pm, c->stream));
   }
   else VC_HIP(c, vc::launch_casc_sqp(a, c->N, c->p.casc.horizon_pm, c->stream));
-  if (flags == VC_HOST_PTRS) return unstage(c, slots);
-  return 0;
+  return st.finish();
 }
 
 // Dynamic single-track SQP, fp64 (st_sqp.hip, stagewise Riccati interior point): xbar has
@@ -289,54 +338,26 @@ int st_solve(vc_ctx* c, int B, const void* x0, const void* kappa, const void* ds
   a.w = w;
   a.qp = c->p.qp;
   a.obs = c->p.obs;
-  std::vector<Slot> slots;
-  if (flags == VC_HOST_PTRS) {
-    slots = {{x0, nullptr, (size_t)B * nx * 8, nullptr},
-             {kappa, nullptr, (size_t)B * N * 8, nullptr},
-             {ds, nullptr, (size_t)B * N * 8, nullptr},
-             {ubar, ubar, (size_t)B * N * nu * 8, nullptr},
-             {nullptr, xbar, (size_t)B * N * nx * 8, nullptr},
-             {nullptr, u0, (size_t)B * nu * 8, nullptr},
-             {nullptr, status, (size_t)B * 4, nullptr},
-             {nullptr, iters, (size_t)B * 4, nullptr},
-             {nullptr, diag, diag ? (size_t)B * VC_ST_DIAG_COLS * 8 : 0, nullptr}};
-    if (int r = stage(c, slots)) return r;
-    a.x0 = (const double*)slots[0].dev;
-    a.kappa = (const double*)slots[1].dev;
-    a.ds = (const double*)slots[2].dev;
-    a.ubar = (const double*)slots[3].dev;
-    a.u_out = (double*)slots[3].dev;
-    a.x_out = (double*)slots[4].dev;
-    a.u0 = (double*)slots[5].dev;
-    a.status = (int32_t*)slots[6].dev;
-    a.iters = (int32_t*)slots[7].dev;
-    a.diag = diag ? (double*)slots[8].dev : nullptr;
-  } else {
-    a.x0 = (const double*)x0;
-    a.kappa = (const double*)kappa;
-    a.ds = (const double*)ds;
-    a.ubar = (const double*)ubar;
-    a.u_out = (double*)ubar;
-    a.x_out = (double*)xbar;
-    a.u0 = (double*)u0;
-    a.status = status;
-    a.iters = iters;
-    a.diag = (double*)diag;
-  }
+  Staging st(c, flags);
+  if (int r = st.bind([&] {
+        a.x0 = st.in(x0, (size_t)B * nx * 8);
+        a.kappa = st.in(kappa, (size_t)B * N * 8);
+        a.ds = st.in(ds, (size_t)B * N * 8);
+        a.ubar = a.u_out = st.inout(ubar, (size_t)B * N * nu * 8);
+        a.x_out = st.out(xbar, (size_t)B * N * nx * 8);
+        a.u0 = st.out(u0, (size_t)B * nu * 8);
+        a.status = st.out(status, (size_t)B * 4);
+        a.iters = st.out(iters, (size_t)B * 4);
+        a.diag = st.out(diag, (size_t)B * VC_ST_DIAG_COLS * 8);
+      }))
+    return r;
   if (const size_t jd = vc::st_sqp_jws_doubles(N, B)) {
     if (int r = ensure_scratch(c, &c->jw, &c->jw_bytes, (size_t)B * jd * 8)) return r;
     a.jws = (double*)c->jw;
   }
-  if (c->sqp_detect) {
-    a.detect = 1;
-    a.detect_eps = c->sqp_detect_eps;
-    a.farkas = (double*)c->sqp_farkas;
-    a.qp_index = (int32_t*)c->sqp_qp_index;
-    c->sqp_farkas_B = B;
-  }
+  if (arm_detection(c, a, B)) a.qp_index = (int32_t*)c->det.qp_index;
   VC_HIP(c, vc::launch_st_sqp(a, N, c->stream));
-  if (flags == VC_HOST_PTRS) return unstage(c, slots);
-  return 0;
+  return st.finish();
 }
 
 // Dynamic single-track SQP (dyn_sqp.hip), fp32: xbar has N state columns.
@@ -354,46 +375,22 @@ int dyn_solve(vc_ctx* c, int B, const void* x0, const void* kappa, const void* d
   a.w = w;
   a.qp = c->p.qp;
   a.obs = c->p.obs;
-  std::vector<Slot> slots;
-  if (flags == VC_HOST_PTRS) {
-    slots = {{x0, nullptr, (size_t)B * nx * 4, nullptr},
-             {kappa, nullptr, (size_t)B * N * 4, nullptr},
-             {ds, nullptr, (size_t)B * N * 4, nullptr},
-             {ubar, ubar, (size_t)B * N * nu * 4, nullptr},
-             {nullptr, xbar, (size_t)B * N * nx * 4, nullptr},
-             {nullptr, u0, (size_t)B * nu * 4, nullptr},
-             {nullptr, status, (size_t)B * 4, nullptr},
-             {nullptr, iters, (size_t)B * 4, nullptr},
-             {nullptr, diag, diag ? (size_t)B * VC_DYN_DIAG_COLS * 4 : 0, nullptr},
-             {nullptr, dbg, dbg ? (size_t)B * vc::dyn_sqp_debug_stride() * 4 : 0, nullptr}};
-    if (int r = stage(c, slots)) return r;
-    a.dbg = dbg ? (float*)slots[9].dev : nullptr;
-    a.x0 = (const float*)slots[0].dev;
-    a.kappa = (const float*)slots[1].dev;
-    a.ds = (const float*)slots[2].dev;
-    a.ubar = (const float*)slots[3].dev;
-    a.u_out = (float*)slots[3].dev;
-    a.x_out = (float*)slots[4].dev;
-    a.u0 = (float*)slots[5].dev;
-    a.status = (int32_t*)slots[6].dev;
-    a.iters = (int32_t*)slots[7].dev;
-    a.diag = diag ? (float*)slots[8].dev : nullptr;
-  } else {
-    a.x0 = (const float*)x0;
-    a.kappa = (const float*)kappa;
-    a.ds = (const float*)ds;
-    a.ubar = (const float*)ubar;
-    a.u_out = (float*)ubar;
-    a.x_out = (float*)xbar;
-    a.u0 = (float*)u0;
-    a.status = status;
-    a.iters = iters;
-    a.diag = (float*)diag;
-    a.dbg = (float*)dbg;
-  }
+  Staging st(c, flags);
+  if (int r = st.bind([&] {
+        a.x0 = st.in(x0, (size_t)B * nx * 4);
+        a.kappa = st.in(kappa, (size_t)B * N * 4);
+        a.ds = st.in(ds, (size_t)B * N * 4);
+        a.ubar = a.u_out = st.inout(ubar, (size_t)B * N * nu * 4);
+        a.x_out = st.out(xbar, (size_t)B * N * nx * 4);
+        a.u0 = st.out(u0, (size_t)B * nu * 4);
+        a.status = st.out(status, (size_t)B * 4);
+        a.iters = st.out(iters, (size_t)B * 4);
+        a.diag = st.out(diag, (size_t)B * VC_DYN_DIAG_COLS * 4);
+        a.dbg = st.out(dbg, (size_t)B * vc::dyn_sqp_debug_stride() * 4);
+      }))
+    return r;
   VC_HIP(c, vc::launch_dyn_sqp(a, N, c->stream));
-  if (flags == VC_HOST_PTRS) return unstage(c, slots);
-  return 0;
+  return st.finish();
 }
 }  // namespace
 
@@ -483,11 +480,8 @@ void vc_destroy(vc_ctx* c) {
   if (c->sim) (void)hipFree(c->sim);
   if (c->ls) (void)hipFree(c->ls);
   if (c->jw) (void)hipFree(c->jw);
-  if (c->farkas) (void)hipFree(c->farkas);
-  if (c->sqp_farkas) (void)hipFree(c->sqp_farkas);
-  if (c->sqp_qp_index) (void)hipFree(c->sqp_qp_index);
-  if (c->casc_farkas) (void)hipFree(c->casc_farkas);
-  if (c->casc_qp_index) (void)hipFree(c->casc_qp_index);
+  if (c->det.farkas) (void)hipFree(c->det.farkas);
+  if (c->det.qp_index) (void)hipFree(c->det.qp_index);
   if (c->own) (void)hipStreamDestroy(c->own);
   delete c;
 }
@@ -531,33 +525,11 @@ int vc_set_infeasibility(vc_ctx* c, int on, double eps) {
     return fail(c, VC_E_UNSUPPORTED,
                 "vc_set_infeasibility: the stagewise kinematic kernel only (kinematic fp64, N=10..60 step 10); "
                 "model=%d dtype=%d N=%d", c->model, c->dtype, c->N);
-  if (on && !c->farkas) {
-    VC_HIP(c, hipSetDevice(c->device));
-    const size_t bytes = (size_t)(c->max_batch > 0 ? c->max_batch : 1) * (7 * c->N - 3) * 8;
-    VC_HIP(c, hipMalloc(&c->farkas, bytes));
-  }
-  c->detect = on != 0;
-  c->detect_eps = eps > 0.0 ? eps : 1e-9;
-  c->farkas_B = 0;  // no solve has written certificates under this setting yet
-  return 0;
+  return set_detection(c, on, eps, (size_t)(7 * c->N - 3), false);
 }
 
 int vc_get_farkas(vc_ctx* c, int B, void* y, int flags) {
-  if (int r = check_common(c, B, flags)) return r;
-  if (!c->detect || !c->farkas) return fail(c, VC_E_ARG, "vc_get_farkas: infeasibility detection is off");
-  if (c->p.qp.kin_sqp > 0)
-    return fail(c, VC_E_UNSUPPORTED, "vc_get_farkas: kin_sqp > 0 solves several QPs per call");
-  if (B > c->farkas_B) return fail(c, VC_E_ARG, "vc_get_farkas: B=%d exceeds the last solve's %d", B, c->farkas_B);
-  if (!y) return fail(c, VC_E_ARG, "null pointer");
-  if (B == 0) return 0;
-  const size_t bytes = (size_t)B * (7 * c->N - 3) * 8;
-  if (flags == VC_DEVICE_PTRS) {
-    VC_HIP(c, hipMemcpyAsync(y, c->farkas, bytes, hipMemcpyDeviceToDevice, c->stream));
-    return 0;
-  }
-  VC_HIP(c, hipMemcpyAsync(y, c->farkas, bytes, hipMemcpyDeviceToHost, c->stream));
-  VC_HIP(c, hipStreamSynchronize(c->stream));
-  return 0;
+  return get_detection(c, "vc_get_farkas", VC_MODEL_KINEMATIC, B, y, nullptr, false, flags);
 }
 
 int vc_set_sqp_infeasibility(vc_ctx* c, int on, double eps) {
@@ -568,35 +540,12 @@ int vc_set_sqp_infeasibility(vc_ctx* c, int on, double eps) {
                 "model=%d dtype=%d N=%d", c->model, c->dtype, c->N);
   if (!(c->p.dyn_mpc.trust_Fx > 0))
     return fail(c, VC_E_ARG, "vc_set_sqp_infeasibility: dyn_mpc.trust_Fx must be > 0 (it bounds |dz|_1)");
-  if (on && !c->sqp_farkas) {
-    VC_HIP(c, hipSetDevice(c->device));
-    const size_t nb = (size_t)(c->max_batch > 0 ? c->max_batch : 1);
-    VC_HIP(c, hipMalloc(&c->sqp_farkas, nb * (12 * c->N - 3) * 8));
-    VC_HIP(c, hipMalloc(&c->sqp_qp_index, nb * 4));
-  }
-  c->sqp_detect = on != 0;
-  c->sqp_detect_eps = eps > 0.0 ? eps : 1e-9;
-  c->sqp_farkas_B = 0;  // no solve has written certificates under this setting yet
-  return 0;
+  return set_detection(c, on, eps, (size_t)(12 * c->N - 3), true);
 }
 
 int vc_get_sqp_farkas(vc_ctx* c, int B, void* y, int32_t* qp_index, int flags) {
-  if (int r = check_common(c, B, flags)) return r;
-  if (!c->sqp_detect || !c->sqp_farkas || !c->sqp_qp_index)
-    return fail(c, VC_E_ARG, "vc_get_sqp_farkas: infeasibility detection is off");
-  if (B > c->sqp_farkas_B)
-    return fail(c, VC_E_ARG, "vc_get_sqp_farkas: B=%d exceeds the last solve's %d", B, c->sqp_farkas_B);
-  if (!y) return fail(c, VC_E_ARG, "null pointer");
-  if (B == 0) return 0;
-  const hipMemcpyKind kind = flags == VC_DEVICE_PTRS ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-  VC_HIP(c, hipMemcpyAsync(y, c->sqp_farkas, (size_t)B * (12 * c->N - 3) * 8, kind, c->stream));
-  if (qp_index) VC_HIP(c, hipMemcpyAsync(qp_index, c->sqp_qp_index, (size_t)B * 4, kind, c->stream));
-  if (flags != VC_DEVICE_PTRS) VC_HIP(c, hipStreamSynchronize(c->stream));
-  return 0;
+  return get_detection(c, "vc_get_sqp_farkas", VC_MODEL_DYNAMIC, B, y, qp_index, true, flags);
 }
-
-// rows of a cascaded QP in oracle/casc_sqp.py casc_qp's order: 12N - 3 single-track, 6 per point-mass stage
-static size_t casc_rows(const vc_ctx* c) { return (size_t)(12 * c->N - 3 + 6 * c->p.casc.horizon_pm); }
 
 int vc_set_casc_infeasibility(vc_ctx* c, int on, double eps) {
   if (!c) return VC_E_ARG;
@@ -610,31 +559,12 @@ int vc_set_casc_infeasibility(vc_ctx* c, int on, double eps) {
                 "vc_set_casc_infeasibility: qp.solver=2 asks for the condensed kernel, which has no detection");
   if (!(c->p.dyn_mpc.trust_Fx > 0))
     return fail(c, VC_E_ARG, "vc_set_casc_infeasibility: dyn_mpc.trust_Fx must be > 0 (it bounds |dz|_1)");
-  if (on && !c->casc_farkas) {
-    VC_HIP(c, hipSetDevice(c->device));
-    const size_t nb = (size_t)(c->max_batch > 0 ? c->max_batch : 1);
-    VC_HIP(c, hipMalloc(&c->casc_farkas, nb * casc_rows(c) * 8));
-    VC_HIP(c, hipMalloc(&c->casc_qp_index, nb * 4));
-  }
-  c->casc_detect = on != 0;
-  c->casc_detect_eps = eps > 0.0 ? eps : 1e-9;
-  c->casc_farkas_B = 0;  // no solve has written certificates under this setting yet
-  return 0;
+  // rows in oracle/casc_sqp.py casc_qp's order: 12N - 3 single-track, 6 per point-mass stage
+  return set_detection(c, on, eps, (size_t)(12 * c->N - 3 + 6 * c->p.casc.horizon_pm), true);
 }
 
 int vc_get_casc_farkas(vc_ctx* c, int B, void* y, int32_t* qp_index, int flags) {
-  if (int r = check_common(c, B, flags)) return r;
-  if (!c->casc_detect || !c->casc_farkas || !c->casc_qp_index)
-    return fail(c, VC_E_ARG, "vc_get_casc_farkas: infeasibility detection is off");
-  if (B > c->casc_farkas_B)
-    return fail(c, VC_E_ARG, "vc_get_casc_farkas: B=%d exceeds the last solve's %d", B, c->casc_farkas_B);
-  if (!y) return fail(c, VC_E_ARG, "null pointer");
-  if (B == 0) return 0;
-  const hipMemcpyKind kind = flags == VC_DEVICE_PTRS ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-  VC_HIP(c, hipMemcpyAsync(y, c->casc_farkas, (size_t)B * casc_rows(c) * 8, kind, c->stream));
-  if (qp_index) VC_HIP(c, hipMemcpyAsync(qp_index, c->casc_qp_index, (size_t)B * 4, kind, c->stream));
-  if (flags != VC_DEVICE_PTRS) VC_HIP(c, hipStreamSynchronize(c->stream));
-  return 0;
+  return get_detection(c, "vc_get_casc_farkas", VC_MODEL_CASCADED, B, y, qp_index, true, flags);
 }
 
 static int kin_solve(vc_ctx* c, int B, const void* x0, const void* kappa, const void* ds, void* xbar,
@@ -693,51 +623,29 @@ static int kin_solve(vc_ctx* c, int B, const void* x0, const void* kappa, const 
   a.w = c->p.kin_mpc;
   a.qp = c->p.qp;
   a.obs = c->p.obs;
-  std::vector<Slot> slots;
-  if (flags == VC_HOST_PTRS) {
-    slots = {{x0, nullptr, (size_t)B * nx * 8, nullptr},
-             {kappa, nullptr, (size_t)B * N * 8, nullptr},
-             {ds, nullptr, (size_t)B * N * 8, nullptr},
-             {ubar_in, u_out, (size_t)B * N * nu * 8, nullptr},
-             {c->p.qp.ms ? xbar : nullptr, xbar, (size_t)B * (N + 1) * nx * 8, nullptr},
-             {nullptr, u0, (size_t)B * nu * 8, nullptr},
-             {nullptr, status, (size_t)B * 4, nullptr},
-             {nullptr, iters, (size_t)B * 4, nullptr},
-             {nullptr, diag, diag ? (size_t)B * VC_DIAG_COLS * 8 : 0, nullptr}};
-    if (int r = stage(c, slots)) return r;
-    a.x0 = (const double*)slots[0].dev;
-    a.kappa = (const double*)slots[1].dev;
-    a.ds = (const double*)slots[2].dev;
-    a.ubar = (const double*)slots[3].dev;
-    a.u_out = (double*)slots[3].dev;
-    a.x_out = (double*)slots[4].dev;
-    a.u0 = (double*)slots[5].dev;
-    a.status = (int32_t*)slots[6].dev;
-    a.iters = (int32_t*)slots[7].dev;
-    a.diag = diag ? (double*)slots[8].dev : nullptr;
-  } else {
-    a.x0 = (const double*)x0;
-    a.kappa = (const double*)kappa;
-    a.ds = (const double*)ds;
-    a.ubar = (const double*)ubar_in;
-    a.u_out = (double*)u_out;
-    a.x_out = (double*)xbar;
-    a.u0 = (double*)u0;
-    a.status = status;
-    a.iters = iters;
-    a.diag = (double*)diag;
-  }
-  a.x_in = a.x_out;  // multiple shooting (qp.ms): the warm-start states arrive in xbar
-  if (c->detect) {  // kin_condensed(c) is false then: every launch below is the stagewise kernel's
-    a.detect = 1;
-    a.detect_eps = c->detect_eps;
-    a.farkas = (double*)c->farkas;
-    c->farkas_B = B;
-  }
+  const size_t u_bytes = (size_t)B * N * nu * 8, x_bytes = (size_t)B * (N + 1) * nx * 8;
+  Staging st(c, flags);
+  if (int r = st.bind([&] {
+        a.x0 = st.in(x0, (size_t)B * nx * 8);
+        a.kappa = st.in(kappa, (size_t)B * N * 8);
+        a.ds = st.in(ds, (size_t)B * N * 8);
+        // the warm start comes from ubar_in and u* goes back through u_out: one slice, two host pointers
+        const Staging::Pair u = st.pair(ubar_in, u_out, u_bytes);
+        a.ubar = u.rd;
+        a.u_out = u.wr;
+        // multiple shooting (qp.ms): the warm-start states arrive in xbar
+        a.x_in = a.x_out = st.pair(c->p.qp.ms ? xbar : nullptr, xbar, x_bytes).wr;
+        a.u0 = st.out(u0, (size_t)B * nu * 8);
+        a.status = st.out(status, (size_t)B * 4);
+        a.iters = st.out(iters, (size_t)B * 4);
+        a.diag = st.out(diag, (size_t)B * VC_DIAG_COLS * 8);
+      }))
+    return r;
+  arm_detection(c, a, B);  // kin_condensed(c) is false then: every launch below is the stagewise kernel's
   const int S = c->p.qp.kin_sqp;
   if (S > 0 && (const void*)a.ubar != (const void*)a.u_out) {
-    // the SQP iterates in place: start it on u_out
-    VC_HIP(c, hipMemcpyAsync(a.u_out, a.ubar, (size_t)B * N * nu * 8, hipMemcpyDeviceToDevice, c->stream));
+    // the SQP iterates in place: start it on u_out (device pointers; staged, the two are one slice)
+    VC_HIP(c, hipMemcpyAsync(a.u_out, a.ubar, u_bytes, hipMemcpyDeviceToDevice, c->stream));
     a.ubar = a.u_out;
   }
   if (S <= 0) {  // the LTV-QP contract: one QP step
@@ -745,16 +653,9 @@ static int kin_solve(vc_ctx* c, int B, const void* x0, const void* kappa, const 
     else VC_HIP(c, vc::launch_kin_ric(a, N, c->stream));
   } else {
     // globalised step (oracle/kin_sqp.py): S x { QP step at ubar; merit line search }
-    const size_t o_up = 0, o_st = al256((size_t)B * N * nu * 8), o_it = o_st + al256((size_t)B * 4),
-                 o_xp = o_it + al256((size_t)B * 4), total = o_xp + al256((size_t)B * (N + 1) * nx * 8);
-    if (total > c->ls_bytes) {
-      VC_HIP(c, hipStreamSynchronize(c->stream));
-      if (c->ls) VC_HIP(c, hipFree(c->ls));
-      c->ls = nullptr;
-      c->ls_bytes = 0;
-      VC_HIP(c, hipMalloc(&c->ls, total));
-      c->ls_bytes = total;
-    }
+    const size_t o_up = 0, o_st = al256(u_bytes), o_it = o_st + al256((size_t)B * 4),
+                 o_xp = o_it + al256((size_t)B * 4), total = o_xp + al256(x_bytes);
+    if (int r = ensure_scratch(c, &c->ls, &c->ls_bytes, total)) return r;
     char* base = static_cast<char*>(c->ls);
     vc::KinMeritArgs m{};
     m.x0 = a.x0;
@@ -783,10 +684,8 @@ static int kin_solve(vc_ctx* c, int B, const void* x0, const void* kappa, const 
     const bool elastic_retry = c->p.qp.elastic < 0.0 && !kin_condensed(c);
     if (c->p.qp.elastic < 0.0) a.qp.elastic = 0.0;
     for (int i = 0; i < S; ++i) {
-      VC_HIP(c, hipMemcpyAsync(base + o_up, a.u_out, (size_t)B * N * nu * 8, hipMemcpyDeviceToDevice, c->stream));
-      if (m.ms)
-        VC_HIP(c, hipMemcpyAsync(base + o_xp, a.x_out, (size_t)B * (N + 1) * nx * 8, hipMemcpyDeviceToDevice,
-                                 c->stream));
+      VC_HIP(c, hipMemcpyAsync(base + o_up, a.u_out, u_bytes, hipMemcpyDeviceToDevice, c->stream));
+      if (m.ms) VC_HIP(c, hipMemcpyAsync(base + o_xp, a.x_out, x_bytes, hipMemcpyDeviceToDevice, c->stream));
       if (kin_condensed(c)) VC_HIP(c, vc::launch_kin_ltv(a, N, c->stream));
       else VC_HIP(c, vc::launch_kin_ric(a, N, c->stream));
       if (elastic_retry) {
@@ -804,8 +703,7 @@ static int kin_solve(vc_ctx* c, int B, const void* x0, const void* kappa, const 
       VC_HIP(c, vc::launch_kin_merit(m, c->stream));
     }
   }
-  if (flags == VC_HOST_PTRS) return unstage(c, slots);
-  return 0;
+  return st.finish();
 }
 
 int vc_solve_debug(vc_ctx* c, int B, const void* x0, const void* kappa, const void* ds, void* xbar, void* ubar,
@@ -826,14 +724,15 @@ int vc_debug_rcp(vc_ctx* c, int n, const void* x, void* out, int flags) {
   if (int r = check_common(c, 0, flags)) return r;
   if (!x || !out) return fail(c, VC_E_ARG, "null pointer");
   if (n == 0) return 0;
-  if (flags == VC_DEVICE_PTRS) {
-    VC_HIP(c, vc::launch_rcp_probe(n, (const double*)x, (double*)out, c->stream));
-    return 0;
-  }
-  std::vector<Slot> slots = {{x, nullptr, (size_t)n * 8, nullptr}, {nullptr, out, (size_t)n * 32, nullptr}};
-  if (int r = stage(c, slots)) return r;
-  VC_HIP(c, vc::launch_rcp_probe(n, (const double*)slots[0].dev, (double*)slots[1].dev, c->stream));
-  return unstage(c, slots);
+  Ptr dx, dout;
+  Staging st(c, flags);
+  if (int r = st.bind([&] {
+        dx = st.in(x, (size_t)n * 8);
+        dout = st.out(out, (size_t)n * 32);
+      }))
+    return r;
+  VC_HIP(c, vc::launch_rcp_probe(n, dx, dout, c->stream));
+  return st.finish();
 }
 
 int vc_debug_qp_fault(vc_ctx* c, int sqp_iter, int problem) {
@@ -863,32 +762,18 @@ int vc_condense(vc_ctx* c, int B, const void* x0, const void* ubar, const void* 
   a.w = c->p.kin_mpc;
   a.qp = c->p.qp;
   a.obs = c->p.obs;
-  std::vector<Slot> slots;
-  if (flags == VC_HOST_PTRS) {
-    slots = {{x0, nullptr, (size_t)B * 6 * 8, nullptr},
-             {kappa, nullptr, (size_t)B * N * 8, nullptr},
-             {ds, nullptr, (size_t)B * N * 8, nullptr},
-             {ubar, nullptr, (size_t)B * n * 8, nullptr},
-             {nullptr, H, (size_t)B * n * n * 8, nullptr},
-             {nullptr, g, (size_t)B * n * 8, nullptr}};
-    if (int r = stage(c, slots)) return r;
-    a.x0 = (const double*)slots[0].dev;
-    a.kappa = (const double*)slots[1].dev;
-    a.ds = (const double*)slots[2].dev;
-    a.ubar = (const double*)slots[3].dev;
-    a.H_out = (double*)slots[4].dev;
-    a.g_out = (double*)slots[5].dev;
-  } else {
-    a.x0 = (const double*)x0;
-    a.kappa = (const double*)kappa;
-    a.ds = (const double*)ds;
-    a.ubar = (const double*)ubar;
-    a.H_out = (double*)H;
-    a.g_out = (double*)g;
-  }
+  Staging st(c, flags);
+  if (int r = st.bind([&] {
+        a.x0 = st.in(x0, (size_t)B * 6 * 8);
+        a.kappa = st.in(kappa, (size_t)B * N * 8);
+        a.ds = st.in(ds, (size_t)B * N * 8);
+        a.ubar = st.in(ubar, (size_t)B * n * 8);
+        a.H_out = st.out(H, (size_t)B * n * n * 8);
+        a.g_out = st.out(g, (size_t)B * n * 8);
+      }))
+    return r;
   VC_HIP(c, vc::launch_kin_ltv(a, N, c->stream));
-  if (flags == VC_HOST_PTRS) return unstage(c, slots);
-  return 0;
+  return st.finish();
 }
 
 int vc_rollout(vc_ctx* c, int B, const void* x0, const void* ubar, const void* kappa, const void* ds, void* xbar,
@@ -899,19 +784,18 @@ int vc_rollout(vc_ctx* c, int B, const void* x0, const void* ubar, const void* k
   const int N = c->N, nx = nx_of(c);
   const size_t es = esize(c);
   vc::ModelArgs m = model_args(c, B);
-  if (flags == VC_HOST_PTRS) {
-    std::vector<Slot> slots = {{x0, nullptr, (size_t)B * nx * es, nullptr},
-                               {ubar, nullptr, (size_t)B * N * 2 * es, nullptr},
-                               {kappa, nullptr, (size_t)B * N * es, nullptr},
-                               {ds, nullptr, (size_t)B * N * es, nullptr},
-                               {nullptr, xbar, (size_t)B * (N + 1) * nx * es, nullptr}};
-    if (int r = stage(c, slots)) return r;
-    VC_HIP(c, vc::launch_rollout(m, c->dtype, slots[0].dev, slots[1].dev, slots[2].dev, slots[3].dev, slots[4].dev,
-                                 c->stream));
-    return unstage(c, slots);
-  }
-  VC_HIP(c, vc::launch_rollout(m, c->dtype, x0, ubar, kappa, ds, xbar, c->stream));
-  return 0;
+  Ptr dx0, dubar, dkappa, dds, dxbar;
+  Staging st(c, flags);
+  if (int r = st.bind([&] {
+        dx0 = st.in(x0, (size_t)B * nx * es);
+        dubar = st.in(ubar, (size_t)B * N * 2 * es);
+        dkappa = st.in(kappa, (size_t)B * N * es);
+        dds = st.in(ds, (size_t)B * N * es);
+        dxbar = st.out(xbar, (size_t)B * (N + 1) * nx * es);
+      }))
+    return r;
+  VC_HIP(c, vc::launch_rollout(m, c->dtype, dx0, dubar, dkappa, dds, dxbar, c->stream));
+  return st.finish();
 }
 
 int vc_linearize(vc_ctx* c, int B, const void* xbar, const void* ubar, const void* kappa, const void* ds, void* A,
@@ -923,20 +807,19 @@ int vc_linearize(vc_ctx* c, int B, const void* xbar, const void* ubar, const voi
   if (B == 0) return 0;
   const int N = c->N;
   vc::ModelArgs m = model_args(c, B);
-  if (flags == VC_HOST_PTRS) {
-    std::vector<Slot> slots = {{xbar, nullptr, (size_t)B * (N + 1) * 6 * 8, nullptr},
-                               {ubar, nullptr, (size_t)B * N * 2 * 8, nullptr},
-                               {kappa, nullptr, (size_t)B * N * 8, nullptr},
-                               {ds, nullptr, (size_t)B * N * 8, nullptr},
-                               {nullptr, A, (size_t)B * N * 36 * 8, nullptr},
-                               {nullptr, Bm, (size_t)B * N * 12 * 8, nullptr}};
-    if (int r = stage(c, slots)) return r;
-    VC_HIP(c, vc::launch_kin_linearize(m, slots[0].dev, slots[1].dev, slots[2].dev, slots[3].dev, slots[4].dev,
-                                       slots[5].dev, c->stream));
-    return unstage(c, slots);
-  }
-  VC_HIP(c, vc::launch_kin_linearize(m, xbar, ubar, kappa, ds, A, Bm, c->stream));
-  return 0;
+  Ptr dxbar, dubar, dkappa, dds, dA, dBm;
+  Staging st(c, flags);
+  if (int r = st.bind([&] {
+        dxbar = st.in(xbar, (size_t)B * (N + 1) * 6 * 8);
+        dubar = st.in(ubar, (size_t)B * N * 2 * 8);
+        dkappa = st.in(kappa, (size_t)B * N * 8);
+        dds = st.in(ds, (size_t)B * N * 8);
+        dA = st.out(A, (size_t)B * N * 36 * 8);
+        dBm = st.out(Bm, (size_t)B * N * 12 * 8);
+      }))
+    return r;
+  VC_HIP(c, vc::launch_kin_linearize(m, dxbar, dubar, dkappa, dds, dA, dBm, c->stream));
+  return st.finish();
 }
 
 int vc_plant_step(vc_ctx* c, int B, const void* x, const void* u, const void* kappa, double dt, void* x_next,
@@ -947,18 +830,17 @@ int vc_plant_step(vc_ctx* c, int B, const void* x, const void* u, const void* ka
   const int nx = nx_of(c);
   const size_t es = esize(c);
   vc::ModelArgs m = model_args(c, B);
-  if (flags == VC_HOST_PTRS) {
-    std::vector<Slot> slots = {{x, nullptr, (size_t)B * nx * es, nullptr},
-                               {u, nullptr, (size_t)B * 2 * es, nullptr},
-                               {kappa, nullptr, (size_t)B * es, nullptr},
-                               {nullptr, x_next, (size_t)B * nx * es, nullptr}};
-    if (int r = stage(c, slots)) return r;
-    VC_HIP(c, vc::launch_plant_step(m, c->dtype, slots[0].dev, slots[1].dev, slots[2].dev, dt, slots[3].dev,
-                                    c->stream));
-    return unstage(c, slots);
-  }
-  VC_HIP(c, vc::launch_plant_step(m, c->dtype, x, u, kappa, dt, x_next, c->stream));
-  return 0;
+  Ptr dx, du, dkappa, dnext;
+  Staging st(c, flags);
+  if (int r = st.bind([&] {
+        dx = st.in(x, (size_t)B * nx * es);
+        du = st.in(u, (size_t)B * 2 * es);
+        dkappa = st.in(kappa, (size_t)B * es);
+        dnext = st.out(x_next, (size_t)B * nx * es);
+      }))
+    return r;
+  VC_HIP(c, vc::launch_plant_step(m, c->dtype, dx, du, dkappa, dt, dnext, c->stream));
+  return st.finish();
 }
 
 int vc_ode(vc_ctx* c, int B, const void* x, const void* u, const void* kappa, int space, void* f, int flags) {
@@ -969,17 +851,17 @@ int vc_ode(vc_ctx* c, int B, const void* x, const void* u, const void* kappa, in
   const int nx = nx_of(c);
   const size_t es = esize(c);
   vc::ModelArgs m = model_args(c, B);
-  if (flags == VC_HOST_PTRS) {
-    std::vector<Slot> slots = {{x, nullptr, (size_t)B * nx * es, nullptr},
-                               {u, nullptr, (size_t)B * 2 * es, nullptr},
-                               {kappa, nullptr, (size_t)B * es, nullptr},
-                               {nullptr, f, (size_t)B * nx * es, nullptr}};
-    if (int r = stage(c, slots)) return r;
-    VC_HIP(c, vc::launch_ode(m, c->dtype, slots[0].dev, slots[1].dev, slots[2].dev, space, slots[3].dev, c->stream));
-    return unstage(c, slots);
-  }
-  VC_HIP(c, vc::launch_ode(m, c->dtype, x, u, kappa, space, f, c->stream));
-  return 0;
+  Ptr dx, du, dkappa, df;
+  Staging st(c, flags);
+  if (int r = st.bind([&] {
+        dx = st.in(x, (size_t)B * nx * es);
+        du = st.in(u, (size_t)B * 2 * es);
+        dkappa = st.in(kappa, (size_t)B * es);
+        df = st.out(f, (size_t)B * nx * es);
+      }))
+    return r;
+  VC_HIP(c, vc::launch_ode(m, c->dtype, dx, du, dkappa, space, df, c->stream));
+  return st.finish();
 }
 
 int vc_spatial_step(vc_ctx* c, int B, const void* x, const void* u, const void* kappa, const void* ds, void* x_next,
@@ -990,19 +872,18 @@ int vc_spatial_step(vc_ctx* c, int B, const void* x, const void* u, const void* 
   const int nx = nx_of(c);
   const size_t es = esize(c);
   vc::ModelArgs m = model_args(c, B);
-  if (flags == VC_HOST_PTRS) {
-    std::vector<Slot> slots = {{x, nullptr, (size_t)B * nx * es, nullptr},
-                               {u, nullptr, (size_t)B * 2 * es, nullptr},
-                               {kappa, nullptr, (size_t)B * es, nullptr},
-                               {ds, nullptr, (size_t)B * es, nullptr},
-                               {nullptr, x_next, (size_t)B * nx * es, nullptr}};
-    if (int r = stage(c, slots)) return r;
-    VC_HIP(c, vc::launch_spatial_step(m, c->dtype, slots[0].dev, slots[1].dev, slots[2].dev, slots[3].dev,
-                                      slots[4].dev, c->stream));
-    return unstage(c, slots);
-  }
-  VC_HIP(c, vc::launch_spatial_step(m, c->dtype, x, u, kappa, ds, x_next, c->stream));
-  return 0;
+  Ptr dx, du, dkappa, dds, dnext;
+  Staging st(c, flags);
+  if (int r = st.bind([&] {
+        dx = st.in(x, (size_t)B * nx * es);
+        du = st.in(u, (size_t)B * 2 * es);
+        dkappa = st.in(kappa, (size_t)B * es);
+        dds = st.in(ds, (size_t)B * es);
+        dnext = st.out(x_next, (size_t)B * nx * es);
+      }))
+    return r;
+  VC_HIP(c, vc::launch_spatial_step(m, c->dtype, dx, du, dkappa, dds, dnext, c->stream));
+  return st.finish();
 }
 
 int vc_track_set(vc_ctx* c, int n_pieces, double h, double length, const double* coef) {
@@ -1030,14 +911,15 @@ int vc_track_k(vc_ctx* c, int B, const void* s, void* k, int flags) {
   if (!c->track) return fail(c, VC_E_ARG, "vc_track_k: no track table (vc_track_set)");
   if (B == 0) return 0;
   const size_t es = esize(c);
-  if (flags == VC_HOST_PTRS) {
-    std::vector<Slot> slots = {{s, nullptr, B * es, nullptr}, {nullptr, k, B * es, nullptr}};
-    if (int r = stage(c, slots)) return r;
-    VC_HIP(c, vc::launch_track_k(track_table(c), c->dtype, B, slots[0].dev, slots[1].dev, c->stream));
-    return unstage(c, slots);
-  }
-  VC_HIP(c, vc::launch_track_k(track_table(c), c->dtype, B, s, k, c->stream));
-  return 0;
+  Ptr dpos, dk;
+  Staging st(c, flags);
+  if (int r = st.bind([&] {
+        dpos = st.in(s, B * es);
+        dk = st.out(k, B * es);
+      }))
+    return r;
+  VC_HIP(c, vc::launch_track_k(track_table(c), c->dtype, B, dpos, dk, c->stream));
+  return st.finish();
 }
 
 int vc_horizon(vc_ctx* c, int B, const void* x0, const void* xbar, double mpc_dt, void* kappa, void* ds,
@@ -1049,19 +931,18 @@ int vc_horizon(vc_ctx* c, int B, const void* x0, const void* xbar, double mpc_dt
   const int N = c->N, nx = nx_of(c), NS = ns_of(c), NH = nh_of(c), M = NH - N;
   const double ds_pm = c->p.casc.ds_pm;
   const size_t es = esize(c);
-  if (flags == VC_HOST_PTRS) {
-    std::vector<Slot> slots = {{x0, nullptr, (size_t)B * nx * es, nullptr},
-                               {xbar, nullptr, (size_t)B * NS * nx * es, nullptr},
-                               {nullptr, kappa, (size_t)B * NH * es, nullptr},
-                               {nullptr, ds, (size_t)B * NH * es, nullptr}};
-    if (int r = stage(c, slots)) return r;
-    VC_HIP(c, vc::launch_horizon(track_table(c), c->model, c->dtype, B, N, M, ds_pm, slots[0].dev, c->dtype == VC_F64,
-                                 slots[1].dev, mpc_dt, slots[2].dev, slots[3].dev, nullptr, c->stream));
-    return unstage(c, slots);
-  }
-  VC_HIP(c, vc::launch_horizon(track_table(c), c->model, c->dtype, B, N, M, ds_pm, x0, c->dtype == VC_F64, xbar,
-                               mpc_dt, kappa, ds, nullptr, c->stream));
-  return 0;
+  Ptr dx0, dxbar, dkappa, dds;
+  Staging st(c, flags);
+  if (int r = st.bind([&] {
+        dx0 = st.in(x0, (size_t)B * nx * es);
+        dxbar = st.in(xbar, (size_t)B * NS * nx * es);
+        dkappa = st.out(kappa, (size_t)B * NH * es);
+        dds = st.out(ds, (size_t)B * NH * es);
+      }))
+    return r;
+  VC_HIP(c, vc::launch_horizon(track_table(c), c->model, c->dtype, B, N, M, ds_pm, dx0, c->dtype == VC_F64, dxbar,
+                               mpc_dt, dkappa, dds, nullptr, c->stream));
+  return st.finish();
 }
 
 int vc_drive(vc_ctx* c, int B, double* x64, const void* u0, double dt, void* x_ctx, int flags) {
@@ -1072,19 +953,17 @@ int vc_drive(vc_ctx* c, int B, double* x64, const void* u0, double dt, void* x_c
   const int nx = nx_of(c);
   const size_t es = esize(c);
   vc::ModelArgs m = model_args(c, B);
-  if (flags == VC_HOST_PTRS) {
-    std::vector<Slot> slots = {{x64, x64, (size_t)B * nx * 8, nullptr},
-                               {u0, nullptr, (size_t)B * 2 * es, nullptr},
-                               {nullptr, x_ctx, x_ctx ? (size_t)B * nx * es : 0, nullptr}};
-    if (int r = stage(c, slots)) return r;
-    VC_HIP(c, vc::launch_drive(m, c->dtype, track_table(c), (double*)slots[0].dev, slots[1].dev, dt,
-                               x_ctx ? slots[2].dev : nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                               nullptr, c->stream));
-    return unstage(c, slots);
-  }
-  VC_HIP(c, vc::launch_drive(m, c->dtype, track_table(c), x64, u0, dt, x_ctx, nullptr, nullptr, nullptr, nullptr,
+  Ptr dx, du0, dctx;
+  Staging st(c, flags);
+  if (int r = st.bind([&] {
+        dx = st.inout(x64, (size_t)B * nx * 8);
+        du0 = st.in(u0, (size_t)B * 2 * es);
+        dctx = st.out(x_ctx, (size_t)B * nx * es);
+      }))
+    return r;
+  VC_HIP(c, vc::launch_drive(m, c->dtype, track_table(c), dx, du0, dt, dctx, nullptr, nullptr, nullptr, nullptr,
                              nullptr, nullptr, nullptr, c->stream));
-  return 0;
+  return st.finish();
 }
 
 int vc_simulate(vc_ctx* c, int B, int steps, double mpc_dt, double dt, double* x64, void* xbar, void* ubar,
@@ -1099,55 +978,40 @@ int vc_simulate(vc_ctx* c, int B, int steps, double mpc_dt, double dt, double* x
   if (B == 0 || steps == 0) return 0;
   const int N = c->N, nx = nx_of(c), NS = ns_of(c), NH = nh_of(c), M = NH - N;
   const double ds_pm = c->p.casc.ds_pm;
-  const size_t es = esize(c);
-  std::vector<Slot> slots;
-  double* dx = x64;
-  void *dxbar = xbar, *dubar = ubar, *dlu = log_u;
-  double* dlx = log_x;
-  int32_t* dnf = nfail;
-  if (flags == VC_HOST_PTRS) {
-    slots = {{x64, x64, (size_t)B * nx * 8, nullptr},
-             {xbar, xbar, (size_t)B * NS * nx * es, nullptr},
-             {ubar, ubar, (size_t)B * NH * 2 * es, nullptr},
-             {nullptr, log_x, log_x ? (size_t)(steps + 1) * B * nx * 8 : 0, nullptr},
-             {nullptr, log_u, log_u ? (size_t)steps * B * 2 * es : 0, nullptr},
-             {nfail, nfail, nfail ? (size_t)B * 4 : 0, nullptr}};
-    if (int r = stage(c, slots)) return r;
-    dx = (double*)slots[0].dev;
-    dxbar = slots[1].dev;
-    dubar = slots[2].dev;
-    dlx = log_x ? (double*)slots[3].dev : nullptr;
-    dlu = log_u ? slots[4].dev : nullptr;
-    dnf = nfail ? (int32_t*)slots[5].dev : nullptr;
-  }
+  const size_t es = esize(c), x_bytes = (size_t)B * nx * 8;
+  double *dx, *dlx;
+  void *dxbar, *dubar, *dlu;
+  int32_t* dnf;
+  Staging st(c, flags);
+  if (int r = st.bind([&] {
+        dx = st.inout(x64, x_bytes);
+        dxbar = st.inout(xbar, (size_t)B * NS * nx * es);
+        dubar = st.inout(ubar, (size_t)B * NH * 2 * es);
+        dlx = st.out(log_x, (size_t)(steps + 1) * B * nx * 8);
+        dlu = st.out(log_u, (size_t)steps * B * 2 * es);
+        dnf = st.inout(nfail, (size_t)B * 4);
+      }))
+    return r;
   // scratch: kappa[B][NH], ds[B][NH], x[B][nx], u0[B][2] (context dtype), status[B], iters[B]
   const size_t o_kap = 0, o_ds = o_kap + al256((size_t)B * NH * es), o_x = o_ds + al256((size_t)B * NH * es),
                o_u0 = o_x + al256((size_t)B * nx * es), o_st = o_u0 + al256((size_t)B * 2 * es),
                o_it = o_st + al256((size_t)B * 4), total = o_it + al256((size_t)B * 4);
-  if (total > c->sim_bytes) {
-    VC_HIP(c, hipStreamSynchronize(c->stream));
-    if (c->sim) VC_HIP(c, hipFree(c->sim));
-    c->sim = nullptr;
-    c->sim_bytes = 0;
-    VC_HIP(c, hipMalloc(&c->sim, total));
-    c->sim_bytes = total;
-  }
+  if (int r = ensure_scratch(c, &c->sim, &c->sim_bytes, total)) return r;
   char* base = static_cast<char*>(c->sim);
   void *kap = base + o_kap, *dsv = base + o_ds, *xc = base + o_x, *u0 = base + o_u0;
-  int32_t *st = (int32_t*)(base + o_st), *it = (int32_t*)(base + o_it);
+  int32_t *stat = (int32_t*)(base + o_st), *it = (int32_t*)(base + o_it);
   const vc::TrackTable tt = track_table(c);
   vc::ModelArgs m = model_args(c, B);
-  if (dlx) VC_HIP(c, hipMemcpyAsync(dlx, dx, (size_t)B * nx * 8, hipMemcpyDeviceToDevice, c->stream));
+  if (dlx) VC_HIP(c, hipMemcpyAsync(dlx, dx, x_bytes, hipMemcpyDeviceToDevice, c->stream));
   for (int step = 0; step < steps; ++step) {
     VC_HIP(c, vc::launch_horizon(tt, c->model, c->dtype, B, N, M, ds_pm, dx, true, dxbar, mpc_dt, kap, dsv, xc,
                                  c->stream));
-    if (int r = vc_solve_diag(c, B, xc, kap, dsv, dxbar, dubar, u0, st, it, nullptr, VC_DEVICE_PTRS)) return r;
-    VC_HIP(c, vc::launch_drive(m, c->dtype, tt, dx, u0, dt, nullptr, st, dxbar, dubar, dnf,
+    if (int r = vc_solve_diag(c, B, xc, kap, dsv, dxbar, dubar, u0, stat, it, nullptr, VC_DEVICE_PTRS)) return r;
+    VC_HIP(c, vc::launch_drive(m, c->dtype, tt, dx, u0, dt, nullptr, stat, dxbar, dubar, dnf,
                                dlx ? dlx + (size_t)(step + 1) * B * nx : nullptr,
                                dlu ? (char*)dlu + (size_t)step * B * 2 * es : nullptr, kap, c->stream));
   }
-  if (flags == VC_HOST_PTRS) return unstage(c, slots);
-  return 0;
+  return st.finish();
 }
 
 }  // extern "C"

@@ -104,27 +104,14 @@ class Context:
         ``VC_INFEASIBLE`` (4), proved by the Farkas vector ``farkas()`` returns; ``eps <= 0`` keeps
         the default roundoff guard 1e-9.  Raises ``VcError`` (VC_E_UNSUPPORTED) on dynamic /
         cascaded contexts."""
-        self._check(self.lib.vc_set_infeasibility(self._h, int(bool(on)), float(eps)))
-        self.detect_infeasible = bool(on)
-        self._last = None
+        self._set_detection(self.lib.vc_set_infeasibility, on, eps)
 
     def farkas(self, B: int | None = None):
         """``vc_get_farkas``: y[B, 7N - 3] of the last solve (rows in the order of
         oracle/ltv_qp.py ``kin_qp``; zero for problems that did not end ``VC_INFEASIBLE``), a
         numpy array after a host-array solve, a torch tensor on the context's device after a
         device-tensor one.  Raises ``VcError`` when the detection is off."""
-        last_B, dev = self._last if self._last is not None else (0, None)
-        B = last_B if B is None else int(B)
-        m = 7 * self.N - 3
-        if dev is not None:
-            import torch
-            y = torch.empty((B, m), dtype=torch.float64, device=dev)
-            ptr, flags = C.c_void_p(y.data_ptr()), _abi.VC_DEVICE_PTRS
-        else:
-            y = np.empty((B, m), np.float64)
-            ptr, flags = C.c_void_p(y.ctypes.data), _abi.VC_HOST_PTRS
-        self._check(self.lib.vc_get_farkas(self._h, B, ptr, flags))
-        return y
+        return self._certificates(self.lib.vc_get_farkas, B, 7 * self.N - 3, False)[0]
 
     def set_sqp_infeasibility(self, on: bool, eps: float = 0.0):
         """``vc_set_sqp_infeasibility``: in-kernel infeasibility detection of the single-track fp64
@@ -133,9 +120,7 @@ class Context:
         only sooner.  Either way ``sqp_farkas()`` returns the proof.  ``eps <= 0`` keeps the default
         guard 1e-9.  Raises ``VcError``: VC_E_UNSUPPORTED on kinematic / cascaded / fp32 contexts,
         VC_E_ARG when ``trust_Fx <= 0``."""
-        self._check(self.lib.vc_set_sqp_infeasibility(self._h, int(bool(on)), float(eps)))
-        self.detect_infeasible = bool(on)
-        self._last = None
+        self._set_detection(self.lib.vc_set_sqp_infeasibility, on, eps)
 
     def sqp_farkas(self, B: int | None = None):
         """``vc_get_sqp_farkas``: ``(y[B, 12N - 3], qp_index[B])`` of the last solve -- rows in the
@@ -143,20 +128,7 @@ class Context:
         infeasible or -1 (``y``'s row is then zero).  Numpy arrays after a host-array solve, torch
         tensors on the context's device after a device-tensor one.  Raises ``VcError`` when the
         detection is off."""
-        last_B, dev = self._last if self._last is not None else (0, None)
-        B = last_B if B is None else int(B)
-        m = 12 * self.N - 3
-        if dev is not None:
-            import torch
-            y = torch.empty((B, m), dtype=torch.float64, device=dev)
-            qi = torch.empty((B,), dtype=torch.int32, device=dev)
-            ptrs, flags = (C.c_void_p(y.data_ptr()), C.c_void_p(qi.data_ptr())), _abi.VC_DEVICE_PTRS
-        else:
-            y = np.empty((B, m), np.float64)
-            qi = np.empty((B,), np.int32)
-            ptrs, flags = (C.c_void_p(y.ctypes.data), C.c_void_p(qi.ctypes.data)), _abi.VC_HOST_PTRS
-        self._check(self.lib.vc_get_sqp_farkas(self._h, B, ptrs[0], ptrs[1], flags))
-        return y, qi
+        return self._certificates(self.lib.vc_get_sqp_farkas, B, 12 * self.N - 3, True)
 
     def set_casc_infeasibility(self, on: bool, eps: float = 0.0):
         """``vc_set_casc_infeasibility``: in-kernel infeasibility detection of the stagewise cascaded
@@ -166,9 +138,7 @@ class Context:
         default guard 1e-9.  Raises ``VcError``: VC_E_UNSUPPORTED on kinematic / dynamic / fp32
         contexts, on tails the stagewise kernel is not built for and with ``qp.solver = 2``;
         VC_E_ARG when ``trust_Fx <= 0``."""
-        self._check(self.lib.vc_set_casc_infeasibility(self._h, int(bool(on)), float(eps)))
-        self.detect_infeasible = bool(on)
-        self._last = None
+        self._set_detection(self.lib.vc_set_casc_infeasibility, on, eps)
 
     def casc_farkas(self, B: int | None = None):
         """``vc_get_casc_farkas``: ``(y[B, 12N - 3 + 6M], qp_index[B])`` of the last solve -- rows in
@@ -176,20 +146,28 @@ class Context:
         whose QP was certified infeasible or -1 (``y``'s row is then zero).  Numpy arrays after a
         host-array solve, torch tensors on the context's device after a device-tensor one.  Raises
         ``VcError`` when the detection is off."""
+        return self._certificates(self.lib.vc_get_casc_farkas, B, 12 * self.N - 3 + 6 * (self.NH - self.N), True)
+
+    def _set_detection(self, fn, on, eps):
+        self._check(fn(self._h, int(bool(on)), float(eps)))
+        self.detect_infeasible = bool(on)
+        self._last = None
+
+    def _certificates(self, fn, B, rows, with_index):
+        """``fn`` (a ``vc_get_*_farkas``) into fresh buffers of the last solve's kind: ``(y[B, rows],)``
+        or, ``with_index``, ``(y, qp_index[B])``."""
         last_B, dev = self._last if self._last is not None else (0, None)
         B = last_B if B is None else int(B)
-        m = 12 * self.N - 3 + 6 * (self.NH - self.N)
         if dev is not None:
             import torch
-            y = torch.empty((B, m), dtype=torch.float64, device=dev)
-            qi = torch.empty((B,), dtype=torch.int32, device=dev)
-            ptrs, flags = (C.c_void_p(y.data_ptr()), C.c_void_p(qi.data_ptr())), _abi.VC_DEVICE_PTRS
+            out = (torch.empty((B, rows), dtype=torch.float64, device=dev),
+                   torch.empty((B,), dtype=torch.int32, device=dev))[:1 + with_index]
+            ptrs, flags = [C.c_void_p(a.data_ptr()) for a in out], _abi.VC_DEVICE_PTRS
         else:
-            y = np.empty((B, m), np.float64)
-            qi = np.empty((B,), np.int32)
-            ptrs, flags = (C.c_void_p(y.ctypes.data), C.c_void_p(qi.ctypes.data)), _abi.VC_HOST_PTRS
-        self._check(self.lib.vc_get_casc_farkas(self._h, B, ptrs[0], ptrs[1], flags))
-        return y, qi
+            out = (np.empty((B, rows), np.float64), np.empty((B,), np.int32))[:1 + with_index]
+            ptrs, flags = [C.c_void_p(a.ctypes.data) for a in out], _abi.VC_HOST_PTRS
+        self._check(fn(self._h, B, *ptrs, flags))
+        return out
 
     def synchronize(self):
         self._check(self.lib.vc_synchronize(self._h))
@@ -233,20 +211,7 @@ class Context:
         the per-problem solver diagnostics as a sixth element."""
         B, N, nx, f = self._batch(x0), self.NH, self.nx, _NP_DT[self.dtype]
         NS = self.ns_solve
-        if xbar is None and self.model == _abi.VC_MODEL_KINEMATIC and self.params.qp.ms:
-            raise ValueError("vc_qp.ms: multiple shooting linearises at the state iterate; pass xbar")
-        if _is_torch(x0):
-            import torch
-            kw = dict(device=x0.device)
-            xbar = torch.empty((B, NS, nx), dtype=x0.dtype, **kw) if xbar is None else xbar
-            u0 = torch.empty((B, NU), dtype=x0.dtype, **kw) if u0 is None else u0
-            status = torch.empty((B,), dtype=torch.int32, **kw) if status is None else status
-            iters = torch.empty((B,), dtype=torch.int32, **kw) if iters is None else iters
-        else:
-            xbar = np.empty((B, NS, nx), f) if xbar is None else xbar
-            u0 = np.empty((B, NU), f) if u0 is None else u0
-            status = np.empty((B,), np.int32) if status is None else status
-            iters = np.empty((B,), np.int32) if iters is None else iters
+        xbar, u0, status, iters = self._solve_outputs(x0, B, xbar, u0, status, iters)
         bufs = [x0, kappa, ds, xbar, ubar, u0, status, iters]
         shapes = [(B, nx), (B, N), (B, N), (B, NS, nx), (B, N, NU), (B, NU), (B,), (B,)]
         dts = [f, f, f, f, f, f, np.int32, np.int32]
@@ -262,11 +227,9 @@ class Context:
         self._check(self.lib.vc_solve(self._h, B, *ptrs, flags))
         return u0, xbar, ubar, status, iters
 
-    def solve_from(self, x0, kappa, ds, ubar_in, u_out, xbar=None, u0=None, status=None, iters=None):
-        """``vc_solve_from``: ``solve`` with the warm start read from ``ubar_in``, which is left
-        unchanged, and u* written to ``u_out``; returns (u0, xbar, u_out, status, iters)."""
-        B, N, nx, f = self._batch(x0), self.NH, self.nx, _NP_DT[self.dtype]
-        NS = self.ns_solve
+    def _solve_outputs(self, x0, B, xbar, u0, status, iters):
+        """The caller's xbar, u0, status, iters, or fresh ones of x0's kind where None."""
+        NS, nx, f = self.ns_solve, self.nx, _NP_DT[self.dtype]
         if xbar is None and self.model == _abi.VC_MODEL_KINEMATIC and self.params.qp.ms:
             raise ValueError("vc_qp.ms: multiple shooting linearises at the state iterate; pass xbar")
         if _is_torch(x0):
@@ -281,6 +244,14 @@ class Context:
             u0 = np.empty((B, NU), f) if u0 is None else u0
             status = np.empty((B,), np.int32) if status is None else status
             iters = np.empty((B,), np.int32) if iters is None else iters
+        return xbar, u0, status, iters
+
+    def solve_from(self, x0, kappa, ds, ubar_in, u_out, xbar=None, u0=None, status=None, iters=None):
+        """``vc_solve_from``: ``solve`` with the warm start read from ``ubar_in``, which is left
+        unchanged, and u* written to ``u_out``; returns (u0, xbar, u_out, status, iters)."""
+        B, N, nx, f = self._batch(x0), self.NH, self.nx, _NP_DT[self.dtype]
+        NS = self.ns_solve
+        xbar, u0, status, iters = self._solve_outputs(x0, B, xbar, u0, status, iters)
         bufs = [x0, kappa, ds, ubar_in, xbar, u_out, u0, status, iters]
         self._last = (B, x0.device if _is_torch(x0) else None)
         shapes = [(B, nx), (B, N), (B, N), (B, N, NU), (B, NS, nx), (B, N, NU), (B, NU), (B,), (B,)]
