@@ -17,7 +17,8 @@
 // LDS holds the Hessian H, the constraint rows of G (broadcast reads), the
 // packed columns of the Cholesky factor (pivot-column broadcast during the
 // factorisation and the transposed solve), and small broadcast vectors:
-// 37.8 KB at N = 20, so four problems fit a CU (B = 1024 fills 256 CUs once).  HBM traffic is only the
+// 39.1 KB at N = 20 (40,032 of the 40,960 bytes that let four problems fit a CU: B = 1024 fills
+// 256 CUs once; static_assert below Smem).  HBM traffic is only the
 // compulsory per-problem inputs and outputs (roofline).
 //
 // Register discipline (checked with `make resources`: no scratch): Mr[n] is the
@@ -86,6 +87,11 @@
 #ifndef KIN_PANEL_CH
 #define KIN_PANEL_CH 6  // columns per in-panel update chunk of factor_blocked, loaded one chunk ahead (2 / 4 / 8:
                         // C2 +1.2 / +1.0 / +0.8 %, bit-identical; profiles/r06/kin_ab/kin_polish_ab_c2_r06ze.log)
+#endif
+
+#ifndef KIN_XPOSE_ONCE
+#define KIN_XPOSE_ONCE 1  // factor_blocked: a panel's tiles go to rows in one LDS round trip (0: one per tile,
+                          // three serial round trips more per factorisation; C2 +1.4 %, bit-identical: profiles/r10)
 #endif
 
 namespace vc {
@@ -264,7 +270,12 @@ struct Smem {
     alignas(16) double tb2[128];  // factor_blocked: last panel's transpose buffer (vz, vc are scratch then)
   };
   double dinv[64];          // inverse pivots 1/L_kk of the current factor (uniform reads)
+#if KIN_XPOSE_ONCE
+  alignas(16) double tb3[8 * 18];  // factor_blocked: panel 1's tile (2,1), 8 real rows at stride 18
+#endif
 };
+// four one-wave workgroups per CU (B = 1024 fills 256 CUs once)
+static_assert(sizeof(Smem<20>) <= 40960, "LDS of one problem: four must fit a CU's 160 KB");
 
 // stage index (1..N-1) of constraint row r
 template <int N>
@@ -591,15 +602,22 @@ __device__ __forceinline__ void build_normal_mfma(double (&Mr)[Dims<N>::n], Smem
 
 // Blocked factorisation of the normal matrix straight from the build's accumulator tiles:
 // panels of 16 columns (the last one 8); for each, the panel's tiles (I, p), I >= p, are moved
-// to this lane's row registers (tile by tile through a 16 x 18 LDS buffer, select-free: lanes
-// outside block row I read the zero row), the panel is factored by the two-column pivot steps
+// to this lane's row registers (every tile to a 16 x 18 LDS buffer of its own, one wave barrier,
+// and each lane reads the row of its own block row's tile: one LDS round trip per panel on the
+// serial chain, where one tile after the other through one buffer paid three, two and one --
+// KIN_XPOSE_ONCE), the panel is factored by the two-column pivot steps
 // described below with the trailing update kept inside the panel, and the tiles to the right,
 // (I, J) with p < J <= I, take the panel's rank-16 update on the matrix cores
 // (v_mfma_f64_16x16x4_f64, operands = the just-stored factor columns from LDS): the trailing
 // update, 880 VALU FMAs + 380 broadcast reads in the row-per-lane factorisation, becomes
 // 16 MFMAs.  Output: s.Lc columns, s.dinv (inverse pivots), Mr = row `lane` of L strictly
-// below the diagonal.  Buffers: panels 0, 1 use the factor storage of columns >= 16 (written
-// only by panel 1's own steps, after its transposes), panel 2 the broadcast vectors (tb2).
+// below the diagonal.  Buffers and what each aliases: panel 0's three tiles lie in s.Lc from its
+// start (720 doubles: no column of this factor is stored yet, and the previous factor's last
+// readers -- the solves, factor_update -- were issued before, LDS executing a wave's operations
+// in order); panel 1's tile (1,1) lies in the storage of columns >= 16 (written only by panel 1's
+// own steps, after its transposes; columns 0..15 are live by then) and its tile (2,1) in s.tb3,
+// which nothing else uses; panel 2's tile lies in the broadcast vectors s.vz / s.vc (tb2), which
+// every caller rewrites before reading.  s.Lc's LC_ZERO slot and s.zrow are never written.
 // Returns false (uniform) if a pivot is not positive.
 // Pivot steps: two columns per step -- the 2x2 diagonal block comes from lanes k, k+1 by
 // readlane, both pivots are taken in registers (rsq_nr), both columns published to LDS, and one
@@ -662,6 +680,43 @@ __device__ bool factor_blocked(double (&Mr)[Dims<N>::n], d4 (&acc)[Tiles<N>::NT]
     // ---- panel columns of this lane's row from tiles (I, p), I >= p
     double* tb = p < 2 ? &s.Lc[lc_start<n>(16)] : &s.tb2[0];
     const int TS = p < 2 ? 18 : 10;  // even stride: 16-byte rows, conflict-free row reads
+#if KIN_XPOSE_ONCE
+    // One LDS round trip per panel: every tile (I, p) goes to a buffer of its own, and a lane
+    // reads the row of its own block row's tile only (lanes of other block rows and the padding
+    // lanes >= n: the zero row).  Panel 0: three buffers 16 x 18 apart from Lc[0] (288 + 288 + 144
+    // doubles; nothing of this factor is stored yet, and the previous factor's readers were issued
+    // before); panel 1: tile (1,1) in the storage of columns >= 16 as before, tile (2,1) in tb3;
+    // panel 2: its one tile in tb2 as before.  Block row 2 has 8 real rows, so its tiles store
+    // 8 rows.  0.0 + v is what the chain of adds onto a zeroed register gave (-0.0 becomes +0.0).
+    static_assert(2 * 16 * 18 + 8 * 18 <= DUMMY, "panel 0's three buffers inside the factor storage");
+    {
+      auto tbuf = [&](int I) -> double* {
+        return p == 0 ? &s.Lc[16 * 18 * I] : (p == 1 ? (I == 1 ? tb : &s.tb3[0]) : tb);
+      };
+      wave_sync();  // the buffers' earlier readers are done
+#pragma unroll
+      for (int I = p; I < NB; ++I) {
+        const int t = I * (I + 1) / 2 + p;
+        double* tbI = tbuf(I);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int r = lr + 4 * q;
+          if (16 * I + 4 * q < n)  // block row 2: rows 8..15 of its tiles are padding
+            tbI[(lc < W ? r * TS + lc : 8 * TS + lc)] = acc[t][q];  // lc >= W: dummy slots past the rows
+        }
+      }
+      wave_sync();
+      const double* own = p == 0 ? &s.Lc[16 * 18 * myI + lc * TS]
+                                 : (p == 1 ? (myI == 1 ? &tb[lc * TS] : &s.tb3[lc * TS]) : &tb[lc * TS]);
+      lds_cd2* src = (lds_cd2*)lds_opaque(myI >= p && lane < n ? own : &s.zrow[0]);
+#pragma unroll
+      for (int i = 0; i < W; i += 2) {
+        const d2 v = src[i / 2];
+        Mr[c0 + i] = 0.0 + v.x;
+        Mr[c0 + i + 1] = 0.0 + v.y;
+      }
+    }
+#else
 #pragma unroll
     for (int i = c0; i < c1; ++i) Mr[i] = 0.0;
 #pragma unroll
@@ -683,6 +738,7 @@ __device__ bool factor_blocked(double (&Mr)[Dims<N>::n], d4 (&acc)[Tiles<N>::NT]
         Mr[c0 + i + 1] += v.y;
       }
     }
+#endif
     wave_sync();  // buffer reads done before the panel's factor stores
     // ---- the panel: two-column pivot steps, trailing update inside the panel
     part(0, c0);
@@ -1191,7 +1247,13 @@ __global__ __launch_bounds__(64) void kin_ltv_kernel(KinLtvArgs A) {
     s.vc[lane] = (lane < NC) ? (cs.lhi - cs.llo) : 0.0;
     wave_sync();
     const double yc = grow_dot<N>(s, lane);
-    rd = (lane < n) ? (h_dot<N>(s, lane) + gj + (bx.lhi - bx.llo) + gt_dot<N>(s, lane)) : 0.0;
+    // H z outside the select's branch, every lane taking part (lanes >= n repeat row 0), G' lambda
+    // inside it: with both inside, the allocator kept two of the loop's values in scratch across
+    // them; with both outside, hundreds of bytes
+    fence();
+    const double hz = h_dot<N>(s, lane);
+    fence();
+    rd = (lane < n) ? (hz + gj + (bx.lhi - bx.llo) + gt_dot<N>(s, lane)) : 0.0;
     rlo_b = bx.hasLo ? (z - bx.lo - bx.slo) : 0.0;
     rhi_b = bx.hasHi ? (bx.hi - z - bx.shi) : 0.0;
     rlo_c = cs.hasLo ? (yc - cs.lo - cs.slo) : 0.0;
@@ -1223,7 +1285,13 @@ __global__ __launch_bounds__(64) void kin_ltv_kernel(KinLtvArgs A) {
       no_hoist();
       VC_TSTAMP(t_res0)
       if (it == 0) true_residuals();
-      const double mu = wave_sum(bx.slo * bx.llo + bx.shi * bx.lhi + cs.slo * cs.llo + cs.shi * cs.lhi) / mtot;
+      // (the first product rounded, the others fused onto it in order: spelled out because the
+      // contraction pass decides by the products' other uses -- code elsewhere in the loop that
+      // names one of these products again moved the rounding and, now and then, sm's last bit:
+      // DESIGN 3.1 round 10)
+      const double mu = wave_sum(__builtin_fma(cs.shi, cs.lhi,
+                                               __builtin_fma(cs.slo, cs.llo,
+                                                             __builtin_fma(bx.shi, bx.lhi, bx.slo * bx.llo)))) / mtot;
       double res = max_residual();
       if (it > 0 && res <= tol_cur && mu <= tol_cur) {
         true_residuals();  // the carried residual would stop here: the true one decides
@@ -1274,12 +1342,20 @@ __global__ __launch_bounds__(64) void kin_ltv_kernel(KinLtvArgs A) {
       for (int pass = 0; pass < 2; ++pass) {
         no_hoist();
         // complementarity residuals: affine (pass 0), Mehrotra corrector (pass 1)
-        const double rclo_b = bx.slo * bx.llo + pp1 - sm, rchi_b = bx.shi * bx.lhi + pp2 - sm;
-        const double rclo_c = cs.slo * cs.llo + pp3 - sm, rchi_c = cs.shi * cs.lhi + pp4 - sm;
-        const double eb = (bx.hasHi ? (-rchi_b * ishi_b - whi_b * rhi_b) : 0.0) +
-                          (bx.hasLo ? (rclo_b * islo_b + wlo_b * rlo_b) : 0.0);
-        const double ec = (cs.hasHi ? (-rchi_c * ishi_c - whi_c * rhi_c) : 0.0) +
-                          (cs.hasLo ? (rclo_c * islo_c + wlo_c * rlo_c) : 0.0);
+        const double rclo_b = __builtin_fma(bx.slo, bx.llo, pp1) - sm, rchi_b = __builtin_fma(bx.shi, bx.lhi, pp2) - sm;
+        const double rclo_c = __builtin_fma(cs.slo, cs.llo, pp3) - sm, rchi_c = __builtin_fma(cs.shi, cs.lhi, pp4) - sm;
+        // Which product of each two-product expression below is rounded and which is fused into the
+        // fma is spelled out, as the compiler has chosen it since round 7 (the outputs are pinned
+        // bit for bit): left to the contraction pass, the choice follows how many uses a product
+        // has in sight, and a branch on `pass` around eb / ec changed it (u* moved by 1.5e-10:
+        // DESIGN 3.1 round 10).  thi: rounded, shared by eb / ec and d4 / e4; on the low side
+        // eb / ec round rc * (1/s) and fuse the weight term, d2 / e2 the other way round.
+        const double thi_b = ishi_b * -rchi_b, thi_c = ishi_c * -rchi_c;
+        const double tlo_b = islo_b * rclo_b, tlo_c = islo_c * rclo_c;
+        const double eb = (bx.hasHi ? __builtin_fma(-whi_b, rhi_b, thi_b) : 0.0) +
+                          (bx.hasLo ? __builtin_fma(wlo_b, rlo_b, tlo_b) : 0.0);
+        const double ec = (cs.hasHi ? __builtin_fma(-whi_c, rhi_c, thi_c) : 0.0) +
+                          (cs.hasLo ? __builtin_fma(wlo_c, rlo_c, tlo_c) : 0.0);
         wave_sync();
         s.vc[lane] = (lane < NC) ? ec : 0.0;
         wave_sync();
@@ -1292,13 +1368,14 @@ __global__ __launch_bounds__(64) void kin_ltv_kernel(KinLtvArgs A) {
         wave_sync();
         const double dyc = grow_dot<N>(s, lane);
         const double d1 = bx.hasLo ? dz + rlo_b : 0.0;
-        const double d2 = bx.hasLo ? (-rclo_b * islo_b - wlo_b * (dz + rlo_b)) : 0.0;
+        // (-rclo is - wlo (dz + rlo)) and (-rchi is - whi (rhi - dz)), roundings as noted above
+        const double d2 = bx.hasLo ? __builtin_fma(islo_b, -rclo_b, -(wlo_b * (dz + rlo_b))) : 0.0;
         const double d3 = bx.hasHi ? rhi_b - dz : 0.0;
-        const double d4 = bx.hasHi ? (-rchi_b * ishi_b - whi_b * (rhi_b - dz)) : 0.0;
+        const double d4 = bx.hasHi ? __builtin_fma(-whi_b, rhi_b - dz, thi_b) : 0.0;
         const double e1 = cs.hasLo ? dyc + rlo_c : 0.0;
-        const double e2 = cs.hasLo ? (-rclo_c * islo_c - wlo_c * (dyc + rlo_c)) : 0.0;
+        const double e2 = cs.hasLo ? __builtin_fma(islo_c, -rclo_c, -(wlo_c * (dyc + rlo_c))) : 0.0;
         const double e3 = cs.hasHi ? rhi_c - dyc : 0.0;
-        const double e4 = cs.hasHi ? (-rchi_c * ishi_c - whi_c * (rhi_c - dyc)) : 0.0;
+        const double e4 = cs.hasHi ? __builtin_fma(-whi_c, rhi_c - dyc, thi_c) : 0.0;
         const double tmax = wave_max(fmax(fmax(fmax(-d1 * islo_b, -d2 * illo_b), fmax(-d3 * ishi_b, -d4 * ilhi_b)),
                                           fmax(fmax(-e1 * islo_c, -e2 * illo_c), fmax(-e3 * ishi_c, -e4 * ilhi_c))));
         const double amax = 1.0 / fmax(1.0, tmax);  // largest a in (0, 1] keeping every v + a dv >= 0
