@@ -295,6 +295,32 @@ int vc_set_sqp_infeasibility(vc_ctx* ctx, int on, double eps);
  * exceeds the last solve's batch. */
 int vc_get_sqp_farkas(vc_ctx* ctx, int B, void* y, int32_t* qp_index, int flags);
 
+/* Regularised retry of the single-track SQP's QPs (ABI 13, additive; VC_MODEL_DYNAMIC, VC_F64:
+ * st_sqp.hip, every built N, both tyres, either J placement, with or without
+ * vc_set_sqp_infeasibility).  levels = J in 1..6, factor = f > 1 (factor <= 0 keeps 10): a QP whose
+ * interior point breaks down -- non-finite or overflowed residuals, or a Riccati factorisation that
+ * loses definiteness away from convergence -- is solved again as a fresh QP (the same linearisation,
+ * rows and start point) with the proximal weight qp.prox f^j, j = 1, 2, ... J, in its stage Hessians;
+ * the interior point, the active-set polish and its certificate all see that QP.  The first rung that
+ * does not break down gives the step.  A QP certified infeasible, one that only reaches qp.max_iter
+ * and a converged one start no rung.  When rung J breaks down too, its failure is handled as a
+ * failure always was: in SQP iteration 0 the iterate is applied and the status is VC_MAX_ITER, in a
+ * later one the step is refused and the SQP ends (diag[2] bit 16, status from the earlier QPs).  No
+ * status rule changes; diag[2] gains bit 64 (some QP's ladder was exhausted) and bit 128 (some QP's
+ * applied step came from a level above 0).  iters sums the interior-point iterations of every rung;
+ * diag[3] stays the largest count of one interior-point run.
+ * levels = 0 (the default): off, the context behaves exactly as before.  VC_E_ARG when levels is
+ * outside 0..6 or 0 < factor <= 1; VC_E_UNSUPPORTED on kinematic, cascaded and fp32 contexts and on
+ * horizons st_sqp.hip is not built for. */
+int vc_set_sqp_regularization(vc_ctx* ctx, int levels, double factor);
+
+/* level[B][dyn_mpc.sqp_iters] (int32) of the last vc_solve* on this context, one entry per QP:
+ * 0..J the level its answer came from (a QP certified infeasible: the level at which it was
+ * certified), -1 the QP was not run because the SQP had ended, -2 its ladder was exhausted.  level
+ * follows the pointer convention of `flags`.  VC_E_ARG when the feature is off or B exceeds the last
+ * solve's batch. */
+int vc_get_sqp_regularization(vc_ctx* ctx, int B, int32_t* level, int flags);
+
 /* Infeasibility detection of the cascaded SQP (ABI 13, additive; VC_MODEL_CASCADED, VC_F64, the
  * stagewise kernel casc_ric.hip: N = 20 with horizon_pm = 15 / 25 / 35 / 40, both tyres, either J
  * placement).  on != 0: every QP of the SQP is tested inside its interior point in every iteration
@@ -362,8 +388,11 @@ int vc_solve_from(vc_ctx* ctx, int B, const void* x0, const void* kappa, const v
  * the earlier iterate returned, so `status` reflects the QPs before it only), 32 a QP was certified
  * infeasible by a Farkas vector (single-track fp64 with vc_set_sqp_infeasibility on: with status
  * VC_INFEASIBLE the first QP, with bit 16 a later one; vc_get_sqp_farkas; cascaded fp64 with
- * vc_set_casc_infeasibility on likewise; vc_get_casc_farkas); [3] the largest
- * interior-point iteration count of one QP. */
+ * vc_set_casc_infeasibility on likewise; vc_get_casc_farkas), 64 some QP broke down at every level
+ * of its regularisation ladder, 128 some QP's applied step came from a level above 0 (both only on
+ * single-track fp64 contexts with vc_set_sqp_regularization on; vc_get_sqp_regularization has the
+ * level of every QP); [3] the largest interior-point iteration count of one QP (of one rung, where a
+ * QP was solved again). */
 int vc_solve_diag(vc_ctx* ctx, int B, const void* x0, const void* kappa, const void* ds,
                   void* xbar, void* ubar, void* u0, int32_t* status, int32_t* iters, void* diag,
                   int flags);
@@ -385,6 +414,14 @@ int vc_debug_stride(void);
  * merit line search refuses the step and keeps the previous iterate.  sqp_iter < 0 turns
  * it off (the default).  No reference counterpart. */
 int vc_debug_qp_fault(vc_ctx* ctx, int sqp_iter, int problem);
+
+/* Test hook (single-track fp64 SQP contexts): in the QP of SQP iteration `sqp_iter` (0-based) of
+ * problem `problem`, the rungs 0..levels-1 of the regularisation ladder report a failed Riccati
+ * factorisation at their first interior-point iteration (a flag and-ed with the factorisation's
+ * result: no arithmetic is disturbed), so tests can walk the ladder of vc_set_sqp_regularization on
+ * well-scaled problems.  With the feature off only rung 0 exists and the QP fails as a breakdown
+ * always did.  sqp_iter < 0 turns it off (the default).  No reference counterpart. */
+int vc_debug_sqp_breakdown(vc_ctx* ctx, int sqp_iter, int problem, int levels);
 
 /* Test diagnostics: the reciprocal forms of the solve kernels evaluated on the device for n
  * (<= max_batch) inputs x[n] fp64, out[n][4] fp64: IEEE 1/x, rcp_nr(x) (kin_ltv), the

@@ -27,6 +27,11 @@
 //              region and the w box bound |dz|_1 <= R, so d'y + R |C'y|_inf < 0 proves that no dz exists
 //              (DESIGN.md 11).  The first QP: the problem ends VC_INFEASIBLE at its warm start; a later
 //              one: the existing `stopped` path, only sooner.  y goes to A.farkas, the QP to A.qp_index.
+//   regularise (REG instantiation, vc_set_sqp_regularization; built from st_sqp_reg.hip): a QP whose interior
+//              point leaves through `fail` is solved again from its start point with the proximal weight
+//              prox f^j, j = 1..J, in the stage Hessians; the first rung that does not fail
+//              gives the step, the last rung's failure is handled as a failure always was.  The level of
+//              every QP goes to A.level.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -34,6 +39,11 @@
 
 #include "vc_dual.hpp"
 #include "vc_kernels.hpp"
+
+// 1 in st_sqp_reg.hip, which includes this file: the REG instantiations and launch_st_sqp_reg only
+#ifndef VC_ST_SQP_REG
+#define VC_ST_SQP_REG 0
+#endif
 
 namespace vc {
 namespace {
@@ -293,7 +303,7 @@ __device__ __forceinline__ StJP<N, JG> st_jac(StSmem<N, JG>& s, const StSqpArgs&
   else return s.J;
 }
 
-template <int N, int TYRE, bool JG, bool DET>
+template <int N, int TYRE, bool JG, bool DET, bool REG>
 __global__ __launch_bounds__(WTH) void st_sqp_kernel(StSqpArgs A) {
   static_assert(N >= 2 && N <= WTH, "one lane per stage");
   // occupancy guard (rocprofv3 LDS_Block_Size: 53,248 B ran three one-wave workgroups per CU,
@@ -319,6 +329,11 @@ __global__ __launch_bounds__(WTH) void st_sqp_kernel(StSqpArgs A) {
   }
   if (l < 8) s.xs.at(0, l) = A.x0[(size_t)b * 8 + l];
   if (l == 0) s.flag[0] = VC_SOLVED;
+  if constexpr (REG) {
+    // -1: the QP was not run (the SQP had ended)
+    if (A.level)
+      for (int i = l; i < W.sqp_iters; i += WTH) A.level[(size_t)b * W.sqp_iters + i] = -1;
+  }
 #ifdef VC_TIMING
   uint64_t tacc[ST_NSLOT] = {};
   const uint64_t t_start = __builtin_amdgcn_s_memtime();
@@ -346,6 +361,7 @@ __global__ __launch_bounds__(WTH) void st_sqp_kernel(StSqpArgs A) {
   bool all_conv = true, any_fail = false, stopped = false;  // stopped: a later QP ended the SQP early
   bool all_pol = true;  // every converged QP's answer certified by the active-set polish
   bool cert = false;    // DET: a QP was certified infeasible (its Farkas vector is in A.farkas)
+  bool reg_out = false, reg_used = false;  // REG: a QP's ladder was exhausted / a QP's step came from a level above 0
   double last_res = 0.0, last_mu = 0.0;
   const double tol_r = 1e-10, tol_mu = 1e-13;
 
@@ -1058,158 +1074,195 @@ __global__ __launch_bounds__(WTH) void st_sqp_kernel(StSqpArgs A) {
     double rd_carry = 0.0;
     bool have_rd = false;
     bool kvalid = false;  // s.u.q.K holds this IPM's factorisation (the linearisation aliases it)
+    // REG: the ladder around the interior point.  lev: the rung, prox_l: its proximal weight;
+    // dbg_hit: vc_debug_sqp_breakdown names this QP of this problem
+    [[maybe_unused]] int lev = 0;
+    [[maybe_unused]] double prox_l = A.qp.prox;
+    [[maybe_unused]] const bool dbg_hit = REG && A.dbg_levels > 0 && sq == A.dbg_sqp_iter && b == A.dbg_problem;
+    for (;;) {
 #pragma unroll 1
-    for (; it < A.qp.max_iter; ++it) {
-      // (a) residuals, stage gradients, barrier-augmented stage Hessians
-      ST_STAMP(t_r0)
-      double rp[NR], wg[NR], grk[9], val[NR];
-      double rpm = 0.0, mus = 0.0;
-      row_values(R, vk, val);
-#pragma unroll
-      for (int i = 0; i < NR; ++i) {
-        rp[i] = R.m[i] * (val[i] + sl[i] - R.d[i]);
-        wg[i] = R.m[i] * la[i] / sl[i];
-        rpm = fmax(rpm, fabs(rp[i]));
-        mus += R.m[i] * sl[i] * la[i];
-      }
-      qmul(Qc, vk, grk);
-#pragma unroll
-      for (int e = 0; e < 9; ++e) grk[e] += qc[e];
-      {
-        double ml[NR];
-#pragma unroll
-        for (int i = 0; i < NR; ++i) ml[i] = R.m[i] * la[i];
-        row_adjoint(R, ml, grk);
-      }
-      if (stl) {
-#pragma unroll
-        for (int e = 0; e < 9; ++e) s.u.q.g[k][e] = grk[e];
-        put_qt(wg);
-      } else {
-        rpm = 0.0;
-        mus = 0.0;
-      }
-      WSYNC();
-      rpm = wmax(rpm);
-      const double mu = wsum(mus) / mcount;
-      ST_ACC(ST_RESID, t_r0)
-      ST_STAMP(t_d0)
-      const bool carried = have_rd;
-      double rdm = carried ? rd_carry : dual_residual(kvalid);
-      bool rd_cl = carried || kvalid;
-      ST_ACC(ST_DUAL, t_d0)
-      last_res = fmax(rdm, rpm);
-      last_mu = mu;
-      if constexpr (DET) {
-        // ahead of the three exits through `fail` below (non-finite residuals, factorisation
-        // breakdown: none of them changes the multipliers), so a diverging QP is still labelled
-        if (it >= 1 && farkas_test(grk)) { infeas = true; break; }
-      }
-      if (!(last_res == last_res) || !(mu == mu) || last_res > 1e300) { fail = true; break; }
-      if (have_rd && mu <= 1e2 * tol_mu && fmax(rdm, rpm) <= 1e3 * rtol) {
-        // the carried value would end the loop here or below: take the sweep's
-        rdm = dual_residual(kvalid);
-        rd_cl = kvalid;
-        have_rd = false;
-        last_res = fmax(rdm, rpm);
-        if (!(last_res == last_res) || last_res > 1e300) { fail = true; break; }
-      }
-      if (last_res <= rtol && mu <= tol_mu) { conv = true; break; }
-
-      // (b) Riccati factorisation of H + C'WC
-      ST_STAMP(t_f0)
-      const bool fok = factor();
-      kvalid = kvalid || fok;
-      ST_ACC(ST_FACT, t_f0)
-      if (!fok) {
-        // the barrier-augmented recursion lost definiteness at the numerical floor (weights
-        // ~1e13, cancellation in P = Hxx - Hxu Huu^-1 Hux): a near-converged iterate stands
-        if (mu <= 1e2 * tol_mu && last_res <= 1e3 * rtol) conv = true;
-        else fail = true;
-        break;
-      }
-
-      // (c) predictor: h = gr + C'(W rp - lam)
-      auto set_h = [&](const double* rc_over_s) {
-        if (stl) {
-          double y[NR], hk[9];
-#pragma unroll
-          for (int i = 0; i < NR; ++i) y[i] = R.m[i] * (wg[i] * rp[i] - rc_over_s[i]);
-#pragma unroll
-          for (int e = 0; e < 9; ++e) hk[e] = grk[e];
-          row_adjoint(R, y, hk);
-#pragma unroll
-          for (int e = 0; e < 9; ++e) s.u.q.g[k][e] = hk[e];
-        }
-        WSYNC();
-      };
-      ST_STAMP(t_q0)
-      set_h(la);
-      ST_ACC(ST_STEP, t_q0)
-      ST_STAMP(t_q1)
-      lq_solve();
-      ST_ACC(ST_SOLVE, t_q1)
-      ST_STAMP(t_q2)
-      double dsa[NR], dla[NR], cdv[NR], dvk[9];
-      double amin = 1.0;
-#pragma unroll
-      for (int e = 0; e < 9; ++e) dvk[e] = s.u.q.g[k][e];
-      row_values(R, dvk, cdv);
-#pragma unroll
-      for (int i = 0; i < NR; ++i) {
-        dsa[i] = R.m[i] * (-rp[i] - cdv[i]);
-        dla[i] = R.m[i] * (wg[i] * (cdv[i] + rp[i]) - la[i]);
-        if (stl && R.m[i] > 0.0) amin = fmin(amin, fmin(step_to_bound(sl[i], dsa[i]), step_to_bound(la[i], dla[i])));
-      }
-      amin = wmin(amin);
-      double ms = 0.0;
-      if (stl) {
-#pragma unroll
-        for (int i = 0; i < NR; ++i) ms += R.m[i] * (sl[i] + amin * dsa[i]) * (la[i] + amin * dla[i]);
-      }
-      ms = wsum(ms) / mcount;
-      const double ratio = mu > 0.0 ? fmin(1.0, ms / mu) : 0.0;
-      const double smu = ratio * ratio * ratio * mu;
-
-      // (d) corrector: rc = s lam + ds_a dl_a - sigma mu
-      double rcs[NR];
-#pragma unroll
-      for (int i = 0; i < NR; ++i) rcs[i] = R.m[i] * (sl[i] * la[i] + dsa[i] * dla[i] - smu) / sl[i];
-      set_h(rcs);
-      ST_ACC(ST_STEP, t_q2)
-      ST_STAMP(t_q3)
-      lq_solve();
-      ST_ACC(ST_SOLVE, t_q3)
-      ST_STAMP(t_q4)
-#pragma unroll
-      for (int e = 0; e < 9; ++e) dvk[e] = s.u.q.g[k][e];
-      row_values(R, dvk, cdv);
-      amin = 1.0;
-#pragma unroll
-      for (int i = 0; i < NR; ++i) {
-        dsa[i] = R.m[i] * (-rp[i] - cdv[i]);
-        dla[i] = R.m[i] * (wg[i] * (cdv[i] + rp[i]) - rcs[i]);
-        if (stl && R.m[i] > 0.0) amin = fmin(amin, fmin(step_to_bound(sl[i], dsa[i]), step_to_bound(la[i], dla[i])));
-      }
-      const double alpha = fmin(1.0, 0.99 * wmin(amin));
-      rd_carry = (1.0 - alpha) * rdm;
-      have_rd = rd_cl;  // only closed-loop values are carried
-      if (stl) {
+      for (; it < A.qp.max_iter; ++it) {
+        // (a) residuals, stage gradients, barrier-augmented stage Hessians
+        ST_STAMP(t_r0)
+        double rp[NR], wg[NR], grk[9], val[NR];
+        double rpm = 0.0, mus = 0.0;
+        row_values(R, vk, val);
 #pragma unroll
         for (int i = 0; i < NR; ++i) {
-          if (R.m[i] > 0.0) {
-            sl[i] = fmax(sl[i] + alpha * dsa[i], 1e-300);
-            la[i] = fmax(la[i] + alpha * dla[i], 1e-300);
+          rp[i] = R.m[i] * (val[i] + sl[i] - R.d[i]);
+          wg[i] = R.m[i] * la[i] / sl[i];
+          rpm = fmax(rpm, fabs(rp[i]));
+          mus += R.m[i] * sl[i] * la[i];
+        }
+        qmul(Qc, vk, grk);
+#pragma unroll
+        for (int e = 0; e < 9; ++e) grk[e] += qc[e];
+        {
+          double ml[NR];
+#pragma unroll
+          for (int i = 0; i < NR; ++i) ml[i] = R.m[i] * la[i];
+          row_adjoint(R, ml, grk);
+        }
+        if (stl) {
+#pragma unroll
+          for (int e = 0; e < 9; ++e) s.u.q.g[k][e] = grk[e];
+          put_qt(wg);
+        } else {
+          rpm = 0.0;
+          mus = 0.0;
+        }
+        WSYNC();
+        rpm = wmax(rpm);
+        const double mu = wsum(mus) / mcount;
+        ST_ACC(ST_RESID, t_r0)
+        ST_STAMP(t_d0)
+        const bool carried = have_rd;
+        double rdm = carried ? rd_carry : dual_residual(kvalid);
+        bool rd_cl = carried || kvalid;
+        ST_ACC(ST_DUAL, t_d0)
+        last_res = fmax(rdm, rpm);
+        last_mu = mu;
+        if constexpr (DET) {
+          // ahead of the three exits through `fail` below (non-finite residuals, factorisation
+          // breakdown: none of them changes the multipliers), so a diverging QP is still labelled
+          if (it >= 1 && farkas_test(grk)) { infeas = true; break; }
+        }
+        if (!(last_res == last_res) || !(mu == mu) || last_res > 1e300) { fail = true; break; }
+        if (have_rd && mu <= 1e2 * tol_mu && fmax(rdm, rpm) <= 1e3 * rtol) {
+          // the carried value would end the loop here or below: take the sweep's
+          rdm = dual_residual(kvalid);
+          rd_cl = kvalid;
+          have_rd = false;
+          last_res = fmax(rdm, rpm);
+          if (!(last_res == last_res) || last_res > 1e300) { fail = true; break; }
+        }
+        if (last_res <= rtol && mu <= tol_mu) { conv = true; break; }
+
+        // (b) Riccati factorisation of H + C'WC
+        ST_STAMP(t_f0)
+        bool fok = factor();
+        if constexpr (REG) fok = fok && !(dbg_hit && it == 0 && lev < A.dbg_levels);  // the test hook's breakdown
+        kvalid = kvalid || fok;
+        ST_ACC(ST_FACT, t_f0)
+        if (!fok) {
+          // the barrier-augmented recursion lost definiteness at the numerical floor (weights
+          // ~1e13, cancellation in P = Hxx - Hxu Huu^-1 Hux): a near-converged iterate stands
+          if (mu <= 1e2 * tol_mu && last_res <= 1e3 * rtol) conv = true;
+          else fail = true;
+          break;
+        }
+
+        // (c) predictor: h = gr + C'(W rp - lam)
+        auto set_h = [&](const double* rc_over_s) {
+          if (stl) {
+            double y[NR], hk[9];
+#pragma unroll
+            for (int i = 0; i < NR; ++i) y[i] = R.m[i] * (wg[i] * rp[i] - rc_over_s[i]);
+#pragma unroll
+            for (int e = 0; e < 9; ++e) hk[e] = grk[e];
+            row_adjoint(R, y, hk);
+#pragma unroll
+            for (int e = 0; e < 9; ++e) s.u.q.g[k][e] = hk[e];
           }
+          WSYNC();
+        };
+        ST_STAMP(t_q0)
+        set_h(la);
+        ST_ACC(ST_STEP, t_q0)
+        ST_STAMP(t_q1)
+        lq_solve();
+        ST_ACC(ST_SOLVE, t_q1)
+        ST_STAMP(t_q2)
+        double dsa[NR], dla[NR], cdv[NR], dvk[9];
+        double amin = 1.0;
+#pragma unroll
+        for (int e = 0; e < 9; ++e) dvk[e] = s.u.q.g[k][e];
+        row_values(R, dvk, cdv);
+#pragma unroll
+        for (int i = 0; i < NR; ++i) {
+          dsa[i] = R.m[i] * (-rp[i] - cdv[i]);
+          dla[i] = R.m[i] * (wg[i] * (cdv[i] + rp[i]) - la[i]);
+          if (stl && R.m[i] > 0.0) amin = fmin(amin, fmin(step_to_bound(sl[i], dsa[i]), step_to_bound(la[i], dla[i])));
+        }
+        amin = wmin(amin);
+        double ms = 0.0;
+        if (stl) {
+#pragma unroll
+          for (int i = 0; i < NR; ++i) ms += R.m[i] * (sl[i] + amin * dsa[i]) * (la[i] + amin * dla[i]);
+        }
+        ms = wsum(ms) / mcount;
+        const double ratio = mu > 0.0 ? fmin(1.0, ms / mu) : 0.0;
+        const double smu = ratio * ratio * ratio * mu;
+
+        // (d) corrector: rc = s lam + ds_a dl_a - sigma mu
+        double rcs[NR];
+#pragma unroll
+        for (int i = 0; i < NR; ++i) rcs[i] = R.m[i] * (sl[i] * la[i] + dsa[i] * dla[i] - smu) / sl[i];
+        set_h(rcs);
+        ST_ACC(ST_STEP, t_q2)
+        ST_STAMP(t_q3)
+        lq_solve();
+        ST_ACC(ST_SOLVE, t_q3)
+        ST_STAMP(t_q4)
+#pragma unroll
+        for (int e = 0; e < 9; ++e) dvk[e] = s.u.q.g[k][e];
+        row_values(R, dvk, cdv);
+        amin = 1.0;
+#pragma unroll
+        for (int i = 0; i < NR; ++i) {
+          dsa[i] = R.m[i] * (-rp[i] - cdv[i]);
+          dla[i] = R.m[i] * (wg[i] * (cdv[i] + rp[i]) - rcs[i]);
+          if (stl && R.m[i] > 0.0) amin = fmin(amin, fmin(step_to_bound(sl[i], dsa[i]), step_to_bound(la[i], dla[i])));
+        }
+        const double alpha = fmin(1.0, 0.99 * wmin(amin));
+        rd_carry = (1.0 - alpha) * rdm;
+        have_rd = rd_cl;  // only closed-loop values are carried
+        if (stl) {
+#pragma unroll
+          for (int i = 0; i < NR; ++i) {
+            if (R.m[i] > 0.0) {
+              sl[i] = fmax(sl[i] + alpha * dsa[i], 1e-300);
+              la[i] = fmax(la[i] + alpha * dla[i], 1e-300);
+            }
+          }
+#pragma unroll
+          for (int e = 0; e < 9; ++e) vk[e] += alpha * dvk[e];
+        }
+        WSYNC();
+        ST_ACC(ST_STEP, t_q4)
+      }
+      it_total += it;
+      it_max = max(it_max, it);
+      if constexpr (!REG) break;
+      else {
+        // a rung that left through `fail` (uniform) is followed by the next: the same rows, linearisation
+        // and start point, the proximal weight times reg_factor in the two input diagonals of Qc
+        if (!fail || lev >= A.reg_levels) break;
+        ++lev;
+        const double prox_n = prox_l * A.reg_factor;
+        Qc[Q77] += 2.0 * (prox_n - prox_l);
+        Qc[Q88] += 2.0 * (prox_n - prox_l);
+        prox_l = prox_n;
+#pragma unroll
+        for (int i = 0; i < NR; ++i) {
+          sl[i] = R.m[i] > 0.0 ? fmax(R.d[i], 1.0) : 1.0;
+          la[i] = R.m[i];
         }
 #pragma unroll
-        for (int e = 0; e < 9; ++e) vk[e] += alpha * dvk[e];
+        for (int e = 0; e < 9; ++e) vk[e] = 0.0;
+        it = 0;
+        fail = false;
+        rd_carry = 0.0;
+        have_rd = kvalid = false;
+        WSYNC();
       }
-      WSYNC();
-      ST_ACC(ST_STEP, t_q4)
     }
-    it_total += it;
-    it_max = max(it_max, it);
+    if constexpr (REG) {
+      // the level this QP ended at (a certified QP: the level of its certificate), -2: every rung failed
+      const bool out = fail && A.reg_levels > 0;
+      reg_out = reg_out || out;
+      if (l == 0 && A.level) A.level[(size_t)b * W.sqp_iters + sq] = out ? -2 : lev;
+    }
     if constexpr (DET) {
       // the certificate y = lam / |lam|_1 goes out in the oracle's row order
       if (infeas) {
@@ -1364,6 +1417,7 @@ __global__ __launch_bounds__(WTH) void st_sqp_kernel(StSqpArgs A) {
     }
     all_conv = all_conv && conv;
     any_fail = any_fail || fail;
+    if constexpr (REG) reg_used = reg_used || (lev > 0 && !fail);  // the step below is a regularised QP's
 
     // ---------------- SQP update: ubar += dz, tested by the next rollout ----------------
     // w is projected onto its box: exact at a converged QP (|violation| <= tol_r), and it
@@ -1423,7 +1477,7 @@ __global__ __launch_bounds__(WTH) void st_sqp_kernel(StSqpArgs A) {
       A.diag[(size_t)b * DS + 1] = last_mu;
       A.diag[(size_t)b * DS + 2] =
           double((any_fail ? 1 : 0) | (all_conv ? 2 : 0) | (all_pol ? 4 : 0) | (stopped ? 16 : 0) |
-                 (DET && cert ? 32 : 0));
+                 (DET && cert ? 32 : 0) | (REG && reg_out ? 64 : 0) | (REG && reg_used ? 128 : 0));
       A.diag[(size_t)b * DS + 3] = double(it_max);
     }
   }
@@ -1433,17 +1487,6 @@ __global__ __launch_bounds__(WTH) void st_sqp_kernel(StSqpArgs A) {
 
 // ---- host launcher ---------------------------------------------------------------
 #define VC_ST_HORIZONS(X) X(20) X(30) X(40) X(50) X(60)
-
-bool st_sqp_built(int N) {
-  switch (N) {
-#define VC_CASE(n) case n:
-    VC_ST_HORIZONS(VC_CASE)
-#undef VC_CASE
-    return true;
-    default:
-      return false;
-  }
-}
 
 // J placement per launch (round 5): the LDS-J kernel runs its waves ~10 % faster (no L2 latency in
 // the LQ sweeps), the global-J kernel fits more workgroups per CU (N = 50 / 60: four instead of
@@ -1455,6 +1498,49 @@ bool st_jg_pick(int B) {
   if constexpr (!st_j_global_ok<N>()) return false;
   else return B > wg_per_cu(sizeof(StSmem<N, false>)) * device_cus();
 }
+template <int N, int TYRE, bool REG>
+void st_launch(const StSqpArgs& a, hipStream_t stream) {
+  if constexpr (st_j_global_ok<N>()) {
+    if (st_jg_pick<N>(a.B)) {
+      if (a.detect) hipLaunchKernelGGL((st_sqp_kernel<N, TYRE, true, true, REG>), dim3(a.B), dim3(WTH), 0, stream, a);
+      else hipLaunchKernelGGL((st_sqp_kernel<N, TYRE, true, false, REG>), dim3(a.B), dim3(WTH), 0, stream, a);
+      return;
+    }
+  }
+  if (a.detect) hipLaunchKernelGGL((st_sqp_kernel<N, TYRE, false, true, REG>), dim3(a.B), dim3(WTH), 0, stream, a);
+  else hipLaunchKernelGGL((st_sqp_kernel<N, TYRE, false, false, REG>), dim3(a.B), dim3(WTH), 0, stream, a);
+}
+template <bool REG>
+hipError_t st_dispatch(const StSqpArgs& a, int N, hipStream_t stream) {
+  const bool lin = a.car.tyre == VC_TYRE_LINEAR;
+  switch (N) {
+#define VC_CASE(n)                                            \
+  case n:                                                    \
+    if (lin) st_launch<n, VC_TYRE_LINEAR, REG>(a, stream);   \
+    else st_launch<n, VC_TYRE_FIALA, REG>(a, stream);        \
+    return hipGetLastError();
+    VC_ST_HORIZONS(VC_CASE)
+#undef VC_CASE
+    default:
+      return hipErrorInvalidValue;
+  }
+}
+
+#if VC_ST_SQP_REG
+// this translation unit is st_sqp_reg.hip: the REG instantiations only (launch_st_sqp hands over to it)
+hipError_t launch_st_sqp_reg(const StSqpArgs& a, int N, hipStream_t stream) { return st_dispatch<true>(a, N, stream); }
+#else
+bool st_sqp_built(int N) {
+  switch (N) {
+#define VC_CASE(n) case n:
+    VC_ST_HORIZONS(VC_CASE)
+#undef VC_CASE
+    return true;
+    default:
+      return false;
+  }
+}
+
 // doubles of J workspace per problem a launch of B problems needs: nonzero only where st_jg_pick
 // takes the global-J kernel (a large max_batch no longer allocates it for LDS-J launches)
 size_t st_sqp_jws_doubles(int N, int B) {
@@ -1468,35 +1554,16 @@ size_t st_sqp_jws_doubles(int N, int B) {
       return 0;
   }
 }
-template <int N, int TYRE>
-void st_launch(const StSqpArgs& a, hipStream_t stream) {
-  if constexpr (st_j_global_ok<N>()) {
-    if (st_jg_pick<N>(a.B)) {
-      if (a.detect) hipLaunchKernelGGL((st_sqp_kernel<N, TYRE, true, true>), dim3(a.B), dim3(WTH), 0, stream, a);
-      else hipLaunchKernelGGL((st_sqp_kernel<N, TYRE, true, false>), dim3(a.B), dim3(WTH), 0, stream, a);
-      return;
-    }
-  }
-  if (a.detect) hipLaunchKernelGGL((st_sqp_kernel<N, TYRE, false, true>), dim3(a.B), dim3(WTH), 0, stream, a);
-  else hipLaunchKernelGGL((st_sqp_kernel<N, TYRE, false, false>), dim3(a.B), dim3(WTH), 0, stream, a);
-}
 
 hipError_t launch_st_sqp(const StSqpArgs& a, int N, hipStream_t stream) {
   if (a.B <= 0) return hipSuccess;
   if (st_sqp_jws_doubles(N, a.B) && !a.jws) return hipErrorInvalidValue;  // the workspace the kernel needs
   if (a.detect && (!a.farkas || !a.qp_index)) return hipErrorInvalidValue;
-  const bool lin = a.car.tyre == VC_TYRE_LINEAR;
-  switch (N) {
-#define VC_CASE(n)                                        \
-  case n:                                                \
-    if (lin) st_launch<n, VC_TYRE_LINEAR>(a, stream);    \
-    else st_launch<n, VC_TYRE_FIALA>(a, stream);         \
-    return hipGetLastError();
-    VC_ST_HORIZONS(VC_CASE)
-#undef VC_CASE
-    default:
-      return hipErrorInvalidValue;
-  }
+  if (a.reg_levels > 0 && (!a.level || !(a.reg_factor > 1.0))) return hipErrorInvalidValue;
+  // the ladder, or the test hook's breakdown: the REG instantiations; otherwise the kernels as they were
+  if (a.reg_levels > 0 || a.dbg_levels > 0) return launch_st_sqp_reg(a, N, stream);
+  return st_dispatch<false>(a, N, stream);
 }
+#endif
 
 }  // namespace vc

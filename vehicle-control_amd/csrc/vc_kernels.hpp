@@ -273,6 +273,14 @@ struct StSqpArgs {
   double detect_eps;    // roundoff guard of the test
   double* farkas;       // [B][12N-3] certificate y in the row order of oracle/dyn_sqp.py dyn_qp
   int32_t* qp_index;    // [B] SQP iteration whose QP was certified, -1: none
+  // regularised retry (vc_set_sqp_regularization) and its test hook (vc_debug_sqp_breakdown), appended
+  // likewise; all zero: off, and the launch takes the kernels without either
+  int reg_levels;       // J >= 1: a QP whose interior point fails is solved again with prox f^j, j = 1..J
+  double reg_factor;    // f > 1
+  int32_t* level;       // [B][w.sqp_iters] level of each QP's answer, -1 not run, -2 ladder exhausted
+  int dbg_levels;       // > 0: in QP dbg_sqp_iter of problem dbg_problem the rungs 0..dbg_levels-1
+  int dbg_sqp_iter;     //      report a failed factorisation at their first iteration
+  int dbg_problem;
 };
 
 // Fused cascaded (single-track + point-mass) SQP step (casc_sqp.hip), fp64.
@@ -358,6 +366,8 @@ bool casc_ric_built(int N, int M);
 // doubles per problem of CascSqpArgs.jws for shape (N, M) (0: the kernel keeps its Jacobians in LDS)
 size_t casc_ric_jws_doubles(int N, int M, int B);  // 0: the launch of B problems keeps J in LDS
 hipError_t launch_st_sqp(const StSqpArgs& a, int N, hipStream_t stream);
+// the REG instantiations (st_sqp_reg.hip); launch_st_sqp checks the arguments and hands over
+hipError_t launch_st_sqp_reg(const StSqpArgs& a, int N, hipStream_t stream);
 bool st_sqp_built(int N);
 // doubles per problem of StSqpArgs.jws for horizon N (0: the kernel keeps its Jacobians in LDS)
 size_t st_sqp_jws_doubles(int N, int B);  // 0: the launch of B problems keeps J in LDS

@@ -27,6 +27,17 @@ struct Detect {
   int B = 0;                 // batch of the last solve that wrote them
 };
 
+// Regularised retry of the single-track SQP's QPs (vc_set_sqp_regularization), the levels of the
+// last solve and the breakdown test hook (vc_debug_sqp_breakdown).
+struct Regularize {
+  int levels = 0;            // 0: off
+  double factor = 10.0;
+  void* level = nullptr;     // [B][sqp_iters] int32 of the last solve (grow-only scratch)
+  size_t level_bytes = 0;
+  int B = 0, K = 0;          // batch and sqp_iters of the last solve that wrote it
+  int dbg_sqp_iter = -1, dbg_problem = -1, dbg_levels = 0;
+};
+
 struct vc_ctx {
   int device = 0, model = 0, N = 0, max_batch = 0, dtype = 0;
   vc_params p{};
@@ -45,6 +56,7 @@ struct vc_ctx {
   size_t jw_bytes = 0;
   int fault_iter = -1, fault_problem = -1;  // vc_debug_qp_fault (tests only)
   Detect det;             // vc_set_*_infeasibility (a context has one model, so one state)
+  Regularize reg;         // vc_set_sqp_regularization / vc_debug_sqp_breakdown (single-track fp64 SQP)
   std::string err;
 };
 
@@ -274,6 +286,27 @@ bool arm_detection(vc_ctx* c, Args& a, int B) {
   return true;
 }
 
+// The reg_* / level / dbg_* tail of the single-track SQP kernel's arguments: the ladder where it is on
+// (the level buffer sized for this launch), the test hook where it is armed.
+int arm_regularization(vc_ctx* c, vc::StSqpArgs& a, int B) {
+  Regularize& r = c->reg;
+  if (r.levels > 0) {
+    const int K = c->p.dyn_mpc.sqp_iters;
+    if (int e = ensure_scratch(c, &r.level, &r.level_bytes, (size_t)B * K * 4)) return e;
+    a.reg_levels = r.levels;
+    a.reg_factor = r.factor;
+    a.level = (int32_t*)r.level;
+    r.B = B;
+    r.K = K;
+  }
+  if (r.dbg_sqp_iter >= 0 && r.dbg_levels > 0) {
+    a.dbg_levels = r.dbg_levels;
+    a.dbg_sqp_iter = r.dbg_sqp_iter;
+    a.dbg_problem = r.dbg_problem;
+  }
+  return 0;
+}
+
 // Cascaded single-track + point-mass SQP (casc_sqp.hip), fp64: arrays span H = N + M stages.
 // mode 0: solve (xbar, ubar, u0, status, iters, diag); mode 1: first QP's H, g (H_out, g_out).
 int casc_solve(vc_ctx* c, int B, const void* x0, const void* kappa, const void* ds, void* xbar, void* ubar, void* u0,
@@ -356,6 +389,7 @@ int st_solve(vc_ctx* c, int B, const void* x0, const void* kappa, const void* ds
     a.jws = (double*)c->jw;
   }
   if (arm_detection(c, a, B)) a.qp_index = (int32_t*)c->det.qp_index;
+  if (int r = arm_regularization(c, a, B)) return r;
   VC_HIP(c, vc::launch_st_sqp(a, N, c->stream));
   return st.finish();
 }
@@ -482,6 +516,7 @@ void vc_destroy(vc_ctx* c) {
   if (c->jw) (void)hipFree(c->jw);
   if (c->det.farkas) (void)hipFree(c->det.farkas);
   if (c->det.qp_index) (void)hipFree(c->det.qp_index);
+  if (c->reg.level) (void)hipFree(c->reg.level);
   if (c->own) (void)hipStreamDestroy(c->own);
   delete c;
 }
@@ -545,6 +580,42 @@ int vc_set_sqp_infeasibility(vc_ctx* c, int on, double eps) {
 
 int vc_get_sqp_farkas(vc_ctx* c, int B, void* y, int32_t* qp_index, int flags) {
   return get_detection(c, "vc_get_sqp_farkas", VC_MODEL_DYNAMIC, B, y, qp_index, true, flags);
+}
+
+int vc_set_sqp_regularization(vc_ctx* c, int levels, double factor) {
+  if (!c) return VC_E_ARG;
+  if (c->model != VC_MODEL_DYNAMIC || c->dtype != VC_F64 || !vc::st_sqp_built(c->N))
+    return fail(c, VC_E_UNSUPPORTED,
+                "vc_set_sqp_regularization: the single-track fp64 SQP kernel only (dynamic fp64, N=20..60 step 10); "
+                "model=%d dtype=%d N=%d", c->model, c->dtype, c->N);
+  if (levels < 0 || levels > 6) return fail(c, VC_E_ARG, "vc_set_sqp_regularization: levels=%d outside [0,6]", levels);
+  const double f = factor <= 0.0 ? 10.0 : factor;  // (a NaN factor fails the test below)
+  if (!(f > 1.0)) return fail(c, VC_E_ARG, "vc_set_sqp_regularization: factor=%g must be > 1 (<= 0 keeps 10)", factor);
+  c->reg.levels = levels;
+  c->reg.factor = f;
+  c->reg.B = 0;  // no solve has written levels under this setting yet
+  return 0;
+}
+
+int vc_get_sqp_regularization(vc_ctx* c, int B, int32_t* level, int flags) {
+  if (int r = check_common(c, B, flags)) return r;
+  const Regularize& g = c->reg;
+  if (g.levels <= 0) return fail(c, VC_E_ARG, "vc_get_sqp_regularization: the regularised retry is off");
+  if (B > g.B) return fail(c, VC_E_ARG, "vc_get_sqp_regularization: B=%d exceeds the last solve's %d", B, g.B);
+  if (!level) return fail(c, VC_E_ARG, "null pointer");
+  if (B == 0) return 0;
+  const hipMemcpyKind kind = flags == VC_DEVICE_PTRS ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  VC_HIP(c, hipMemcpyAsync(level, g.level, (size_t)B * g.K * 4, kind, c->stream));
+  if (flags != VC_DEVICE_PTRS) VC_HIP(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int vc_debug_sqp_breakdown(vc_ctx* c, int sqp_iter, int problem, int levels) {
+  if (!c) return VC_E_ARG;
+  c->reg.dbg_sqp_iter = sqp_iter;
+  c->reg.dbg_problem = problem;
+  c->reg.dbg_levels = levels;
+  return 0;
 }
 
 int vc_set_casc_infeasibility(vc_ctx* c, int on, double eps) {

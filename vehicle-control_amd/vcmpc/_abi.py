@@ -99,6 +99,9 @@ PROTOTYPES = {
     "vc_get_farkas": (C.c_int, [_vp, C.c_int, _vp, C.c_int]),
     "vc_set_sqp_infeasibility": (C.c_int, [_vp, C.c_int, C.c_double]),
     "vc_get_sqp_farkas": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int]),
+    "vc_set_sqp_regularization": (C.c_int, [_vp, C.c_int, C.c_double]),
+    "vc_get_sqp_regularization": (C.c_int, [_vp, C.c_int, _vp, C.c_int]),
+    "vc_debug_sqp_breakdown": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int]),
     "vc_set_casc_infeasibility": (C.c_int, [_vp, C.c_int, C.c_double]),
     "vc_get_casc_farkas": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int]),
     "vc_solve": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int]),

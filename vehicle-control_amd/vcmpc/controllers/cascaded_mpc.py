@@ -102,12 +102,18 @@ class BatchedSingleTrackMPC(Controller):
         # back VC_INFEASIBLE, Farkas-certified, instead of applying a diverged iterate
         # (vc_set_sqp_infeasibility); the neutral retry below handles it like any other status != 0
         self.detect_infeasible = bool((config.get("qp") or {}).get("detect_infeasible", False))
+        # qp.regularize_levels (default 0: off; fp64) / qp.regularize_factor (default 10): a QP whose interior
+        # point breaks down is solved again with the proximal weight prox * factor**j, j = 1..levels
+        # (vc_set_sqp_regularization)
+        self.regularize_levels = int((config.get("qp") or {}).get("regularize_levels", 0) or 0)
+        self.regularize_factor = float((config.get("qp") or {}).get("regularize_factor", 0.0) or 0.0)
         self.ctx = Context(model=_abi.VC_MODEL_DYNAMIC, N=self.N, max_batch=self.B, dtype=vdt, device=device,
                            params=make_params(dyn_car=car.config, dyn_mpc=dict(config, qp=dyn_qp_block(config)),
                                               tyre=getattr(car, "tyre", "fiala"),
                                               obstacles=obstacle_list(car, config),
                                               obstacle_inside=bool(config.get("obstacle_inside", False))),
-                           detect_infeasible=self.detect_infeasible)
+                           detect_infeasible=self.detect_infeasible,
+                           regularize_levels=self.regularize_levels, regularize_factor=self.regularize_factor)
         # warm starts: cascaded_mpc.py:72-76
         rng = np.random.RandomState(seed) if seed is not None else np.random
         self.state_prediction = np.ones((self.B, self.ns, self.N))
@@ -117,6 +123,8 @@ class BatchedSingleTrackMPC(Controller):
         self.iters = np.zeros(self.B, np.int32)
         # per vehicle: control steps whose first solve was certified infeasible (qp.detect_infeasible)
         self.infeasible_steps = np.zeros(self.B, np.int64)
+        # per vehicle: control steps whose plan used a QP answered at a level above 0 (qp.regularize_levels)
+        self.regularized_steps = np.zeros(self.B, np.int64)
 
     def command(self, states):
         """states[B, ns] -> actions[B, na] (u*_0 of every problem).
@@ -138,6 +146,10 @@ class BatchedSingleTrackMPC(Controller):
         u0, xbar, ustar, status, iters = self.ctx.solve(x0f, kf, dsf, ubar)
         bad = status != 0
         self.infeasible_steps += status == _abi.VC_INFEASIBLE
+        # a level above 0 in a solve that was kept (a non-solved one is replaced by the neutral retry below)
+        lev = self.ctx.sqp_regularization() if self.regularize_levels > 0 else None
+        if lev is not None:
+            self.regularized_steps += ~bad & (lev > 0).any(axis=1)
         if bad.any():
             # the retry is neutral in its horizon too: ds, kappa from the state prediction x0 at
             # every stage (vc_simulate's restart), not from the previous plan the failed solve used
@@ -147,6 +159,8 @@ class BatchedSingleTrackMPC(Controller):
             r = self.ctx.solve(cast(x0f[idx]), cast(kap_n), cast(ds_n),
                                np.zeros((len(idx), self.N, self.na), self.np_dtype))
             u0[idx], xbar[idx], ustar[idx], status[idx], iters[idx] = r
+            if lev is not None:
+                self.regularized_steps[idx] += (r[3] == 0) & (self.ctx.sqp_regularization() > 0).any(axis=1)
         self.action_prediction = np.swapaxes(ustar, 1, 2).astype(np.float64)
         self.state_prediction = np.swapaxes(xbar, 1, 2).astype(np.float64)
         u0 = u0.astype(np.float64)

@@ -36,7 +36,8 @@ class Context:
 
     def __init__(self, model: int = _abi.VC_MODEL_KINEMATIC, N: int = 20, max_batch: int = 1024,
                  dtype: int = _abi.VC_F64, device: int = 0, params: _abi.vc_params | None = None,
-                 detect_infeasible: bool = False, infeasible_eps: float = 0.0, **cfgs):
+                 detect_infeasible: bool = False, infeasible_eps: float = 0.0,
+                 regularize_levels: int = 0, regularize_factor: float = 0.0, **cfgs):
         self.lib = _abi.load_library()
         self.model, self.N, self.max_batch, self.dtype, self.device = model, int(N), int(max_batch), dtype, device
         self.nx = NX[model]
@@ -51,6 +52,13 @@ class Context:
         self._h = C.c_void_p(h)
         self.detect_infeasible = False
         self._last = None  # (B, device or None) of the last solve: what farkas() returns
+        self.regularize_levels = 0
+        if regularize_levels:
+            try:
+                self.set_sqp_regularization(regularize_levels, regularize_factor)
+            except Exception:
+                self.close()
+                raise
         if detect_infeasible:
             try:
                 # the single-track fp64 SQP has its own entry point (vc_set_sqp_infeasibility)
@@ -129,6 +137,42 @@ class Context:
         tensors on the context's device after a device-tensor one.  Raises ``VcError`` when the
         detection is off."""
         return self._certificates(self.lib.vc_get_sqp_farkas, B, 12 * self.N - 3, True)
+
+    def set_sqp_regularization(self, levels: int, factor: float = 0.0):
+        """``vc_set_sqp_regularization``: the regularised retry of the single-track fp64 SQP
+        (csrc/st_sqp.hip).  ``levels = J`` in 1..6: a QP whose interior point breaks down is solved
+        again with the proximal weight ``prox * factor**j``, j = 1..J, until a rung does not break
+        down (``factor <= 0`` keeps 10); ``levels = 0`` turns it off.  ``sqp_regularization()``
+        returns the level of every QP; diag[2] bit 64 marks an exhausted ladder, bit 128 a step from
+        a level above 0.  Raises ``VcError``: VC_E_UNSUPPORTED on kinematic / cascaded / fp32
+        contexts, VC_E_ARG for ``levels`` outside 0..6 or ``0 < factor <= 1``."""
+        self._check(self.lib.vc_set_sqp_regularization(self._h, int(levels), float(factor)))
+        self.regularize_levels = int(levels)
+        self._last = None
+
+    def sqp_regularization(self, B: int | None = None):
+        """``vc_get_sqp_regularization``: ``level[B, sqp_iters]`` (int32) of the last solve -- per QP
+        the level 0..J its answer came from, -1 where the QP was not run (the SQP had ended), -2
+        where its ladder was exhausted.  A numpy array after a host-array solve, a torch tensor on
+        the context's device after a device-tensor one.  Raises ``VcError`` when the feature is off."""
+        last_B, dev = self._last if self._last is not None else (0, None)
+        B = last_B if B is None else int(B)
+        K = int(self.params.dyn_mpc.sqp_iters)
+        if dev is not None:
+            import torch
+            out = torch.empty((B, K), dtype=torch.int32, device=dev)
+            ptr, flags = C.c_void_p(out.data_ptr()), _abi.VC_DEVICE_PTRS
+        else:
+            out = np.empty((B, K), np.int32)
+            ptr, flags = C.c_void_p(out.ctypes.data), _abi.VC_HOST_PTRS
+        self._check(self.lib.vc_get_sqp_regularization(self._h, B, ptr, flags))
+        return out
+
+    def debug_sqp_breakdown(self, sqp_iter: int, problem: int = 0, levels: int = 1):
+        """``vc_debug_sqp_breakdown`` (test hook): in the QP of SQP iteration ``sqp_iter`` of problem
+        ``problem`` the rungs 0..levels-1 report a failed factorisation at their first
+        interior-point iteration; ``sqp_iter < 0`` turns it off."""
+        self._check(self.lib.vc_debug_sqp_breakdown(self._h, int(sqp_iter), int(problem), int(levels)))
 
     def set_casc_infeasibility(self, on: bool, eps: float = 0.0):
         """``vc_set_casc_infeasibility``: in-kernel infeasibility detection of the stagewise cascaded
