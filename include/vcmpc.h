@@ -415,6 +415,25 @@ int vc_debug_stride(void);
  * it off (the default).  No reference counterpart. */
 int vc_debug_qp_fault(vc_ctx* ctx, int sqp_iter, int problem);
 
+/* Test hook (kinematic fp64 contexts; anything else VC_E_UNSUPPORTED): one launch of the merit
+ * line search of the kinematic SQP step (csrc/kin_merit.hip) on its own, with the weights,
+ * obstacles, wheelbase, horizon and vc_qp.ms of the context and the kernel's diagnostics switched on,
+ * so tests can observe each of its decisions (oracle/kin_sqp.py line_search, line_search_ms).
+ *   in:      x0[B][6], kappa[B][N], ds[B][N]; u_prev[B][N][2] the iterate before the QP step
+ *   in/out:  u[B][N][2]       the QP's u* in, the accepted iterate u_prev + alpha (u* - u_prev) out
+ *            x[B][N+1][6]     out: the rollout of the accepted u; under vc_qp.ms in: the QP's x*,
+ *                             out: the accepted state iterate (or the rollout where that was reset)
+ *            x_prev[B][N+1][6] in, read under vc_qp.ms only (may be NULL otherwise)
+ *            status[B], iters[B]  the QP's in, the step's out (one buffer each, as vc_solve has them)
+ *            st_acc[B], it_acc[B] the accumulators carried from one SQP iteration to the next
+ *   first:   1 on the first SQP iteration (the accumulators are then not read)
+ *   restart: 1: a failed first QP restarts the iterate from the neutral guess (vc_solve: kin_sqp > 1)
+ *   out:     u0[B][2]; ls_diag[B][4] = alpha, phi(u_prev), phi(accepted), directional derivative D
+ * vc_solve itself never asks for ls_diag.  No reference counterpart. */
+int vc_debug_kin_merit(vc_ctx* ctx, int B, const void* x0, const void* kappa, const void* ds, const void* u_prev,
+                       void* u, const void* x_prev, void* x, int32_t* status, int32_t* iters, int32_t* st_acc,
+                       int32_t* it_acc, int first, int restart, void* u0, void* ls_diag, int flags);
+
 /* Test hook (single-track fp64 SQP contexts): in the QP of SQP iteration `sqp_iter` (0-based) of
  * problem `problem`, the rungs 0..levels-1 of the regularisation ladder report a failed Riccati
  * factorisation at their first interior-point iteration (a flag and-ed with the factorisation's

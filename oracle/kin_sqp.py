@@ -97,6 +97,9 @@ def merit(x0, u, kappa, ds, L, W, x=None):
         pdef = RHO_DEF * np.abs(defects(x0, x, u, kappa, ds, L)).sum(axis=(1, 2))
         x = np.array(x, np.float64, copy=True)
         x[:, 0] = x0
+        # s is never a decision variable (s' = 1; ltv_qp.kin_qp and kin_merit.hip alike): whatever
+        # the iterate's s column holds, the obstacle distances are taken at s0 + cumsum ds
+        x[:, 1:, IS] = x[:, :1, IS] + np.cumsum(np.asarray(ds, np.float64), axis=1)
     B, N = u.shape[:2]
     ds = np.asarray(ds, np.float64)
     ey = x[:, 1:N, IEY]
@@ -132,8 +135,9 @@ def merit(x0, u, kappa, ds, L, W, x=None):
     return np.where(inside, phi + pdef, np.inf)
 
 
-def line_search(x0, ubar, dz, kappa, ds, L, W):
-    """(alpha[B], phi0[B], phi_alpha[B], D[B]) of the rule in the module docstring."""
+def line_search(x0, ubar, dz, kappa, ds, L, W, qp_ok=None):
+    """(alpha[B], phi0[B], phi_alpha[B], D[B]) of the rule in the module docstring.  qp_ok[B]
+    given: a QP without a certified solution refuses its step (alpha = 0, phi_alpha = phi0)."""
     ubar = np.asarray(ubar, np.float64)
     phi0 = merit(x0, ubar, kappa, ds, L, W)
     with np.errstate(invalid="ignore"):
@@ -143,6 +147,8 @@ def line_search(x0, ubar, dz, kappa, ds, L, W):
     phia = phi0.copy()
     restore = ~np.isfinite(phi0)   # outside the domain: the largest step back inside it
     done = (D >= 0.0) & ~restore
+    if qp_ok is not None:
+        done |= ~np.asarray(qp_ok, bool)
     a = 1.0
     p1 = None
     for _ in range(LS_STEPS):
@@ -155,6 +161,8 @@ def line_search(x0, ubar, dz, kappa, ds, L, W):
         done |= ok
         a *= 0.5
     nz = noise_step(alpha, phi0, p1, D)
+    if qp_ok is not None:
+        nz &= np.asarray(qp_ok, bool)
     alpha[nz] = 1.0
     phia[nz] = p1[nz]
     return alpha, phi0, phia, D
@@ -174,15 +182,20 @@ def noise_step(alpha, phi0, p1, D):
                 & (p1 <= phi0 + NOISE_PHI * sc))
 
 
-def line_search_ms(x0, ubar, dz, x, dx, kappa, ds, L, W):
+def line_search_ms(x0, ubar, dz, x, dx, kappa, ds, L, W, qp_ok=None):
     """The multiple-shooting line search: per problem, the merit is the single-shooting one
     (the rollout of u) where that is no larger than the multiple-shooting one at the current
     iterate ("roll" mode: the plain SQP of line_search), else merit(..., x=) along (dx, dz).
     Returns (alpha, phi0, phi_alpha, D, reset): reset where the accepted point's rollout has no
-    larger merit than its state iterate (the next state iterate is then that rollout)."""
+    larger merit than its state iterate (the next state iterate is then that rollout).
+    qp_ok[B] given: a QP without a certified solution refuses its step, and everything the step
+    decides -- alpha, phi_alpha and reset -- is what alpha = 0 implies (kin_merit.hip: src = LS + 1)."""
     ubar = np.asarray(ubar, np.float64)
-    ps = lambda a: merit(x0, ubar + a * dz, kappa, ds, L, W)
-    pm = lambda a: merit(x0, ubar + a * dz, kappa, ds, L, W, x=x + a * dx)
+    # alpha = 0 is the iterate itself, not iterate + 0 * step: a failed QP's output may be
+    # non-finite (kin_merit.hip step_to)
+    to = lambda p, d, a: p if a == 0.0 else p + a * d
+    ps = lambda a: merit(x0, to(ubar, dz, a), kappa, ds, L, W)
+    pm = lambda a: merit(x0, to(ubar, dz, a), kappa, ds, L, W, x=to(x, dx, a))
     ps0, pm0 = ps(0.0), pm(0.0)
     roll = np.isfinite(ps0) & (ps0 <= pm0 + TIE * np.abs(pm0))
     sel = lambda vs, vm: np.where(roll, vs, vm)
@@ -195,6 +208,8 @@ def line_search_ms(x0, ubar, dz, x, dx, kappa, ds, L, W):
     pr, pa_m = ps0.copy(), pm0.copy()
     restore = ~np.isfinite(phi0)   # both merits outside the domain: the largest step back inside
     done = (D >= 0.0) & ~restore
+    if qp_ok is not None:
+        done |= ~np.asarray(qp_ok, bool)
     a = 1.0
     first = None
     for _ in range(LS_STEPS):
@@ -209,11 +224,14 @@ def line_search_ms(x0, ubar, dz, x, dx, kappa, ds, L, W):
         done |= ok
         a *= 0.5
     nz = noise_step(alpha, phi0, first[0], D)
+    if qp_ok is not None:
+        nz &= np.asarray(qp_ok, bool)
     alpha[nz] = 1.0
     phia[nz] = first[0][nz]
     pr[nz], pa_m[nz] = first[1][nz], first[2][nz]
     reset = np.isfinite(pr) & (pr <= pa_m + TIE * np.abs(pa_m))
-    line_search_ms.reset_gap = (pr - pa_m) / np.abs(pa_m)   # for tests: how close the reset decision was
+    with np.errstate(invalid="ignore"):
+        line_search_ms.reset_gap = (pr - pa_m) / np.abs(pa_m)   # for tests: how close the reset decision was
     return alpha, phi0, phia, D, reset
 
 
@@ -253,14 +271,14 @@ def kin_sqp_solve(x0, ubar, kappa, ds, L, W, sqp_iters, x_ws=None, elastic=0.0, 
                     sol["kkt"][key][bad] = se["kkt"][key]
             sol["elastic_retry"] = bad
         dz = sol["u_star"] - u
+        # a QP without a certified solution refuses its step (kin_merit.hip qp_ok): the line search
+        # answers alpha = 0 and, under multiple shooting, the reset decision of alpha = 0
+        ok = sol["polished"] | (sol["converged"] & ~sol["diverged"])
         if x is None:
-            alpha, phi0, phia, D = line_search(x0, u, dz, kappa, ds, L, W)
+            alpha, phi0, phia, D = line_search(x0, u, dz, kappa, ds, L, W, qp_ok=ok)
         else:
             dx = sol["x_star"] - x
-            alpha, phi0, phia, D, reset = line_search_ms(x0, u, dz, x, dx, kappa, ds, L, W)
-        # a QP without a certified solution refuses its step (kin_merit.hip qp_ok)
-        ok = sol["polished"] | (sol["converged"] & ~sol["diverged"])
-        alpha = np.where(ok, alpha, 0.0)
+            alpha, phi0, phia, D, reset = line_search_ms(x0, u, dz, x, dx, kappa, ds, L, W, qp_ok=ok)
         hist.append(dict(alpha=alpha, phi0=phi0, phi=phia, D=D, kkt=sol["kkt"], polished=sol["polished"],
                          elastic_retry=sol.get("elastic_retry", np.zeros(len(alpha), bool)), qp_ok=ok))
         # a refused step (alpha = 0) keeps the iterate as it is: u + 0 * dz would carry a failed
@@ -279,6 +297,7 @@ def kin_sqp_solve(x0, ubar, kappa, ds, L, W, sqp_iters, x_ws=None, elastic=0.0, 
             u[~ok] = 0.0
             if x is not None:
                 x[~ok] = np.asarray(x0, np.float64)[~ok, None, :]
+                x[:, 1:, IS] = x0[:, None, IS] + np.cumsum(ds, axis=1)     # s stays s0 + sum ds
             hist[-1]["restart"] = ~ok
     x_star = Q.kin_predict(np.asarray(x0, np.float64), u, kappa, ds, L) if x is None else x
     return dict(u_star=u, x_star=x_star, u0=u[:, 0].copy(), hist=hist)

@@ -176,7 +176,15 @@ __global__ __launch_bounds__(64) void kin_merit_kernel(KinMeritArgs A) {
     const double* xp = A.x_prev + (size_t)b * (N + 1) * KIN_NX;
     for (int e = l; e < (N + 1) * KIN_NX; e += 64)
       if (e < KIN_NX) xo[e] = A.x0[(size_t)b * KIN_NX + e];  // x_0 = x0
-      else if (e % KIN_NX != 2) xo[e] = step_to(xp[e], xo[e], al);  // s stays s0 + sum ds
+      else if (e % KIN_NX != 2) xo[e] = step_to(xp[e], xo[e], al);
+      // s stays s0 + sum ds: the QP's own column as it stands for an accepted step; a refused one
+      // (al = 0) may come from a failed QP whose x* is NaN in every column, so s is summed again
+      // (in kin_ric.hip's order: the same bits as a solved QP's column)
+      else if (al == 0.0) {
+        double sa = A.x0[(size_t)b * KIN_NX + 2];
+        for (int k = 0; k < e / KIN_NX; ++k) sa += A.ds[(size_t)b * N + k];
+        xo[e] = sa;
+      }
   }
   if (l == 0) {  // rollout of the accepted inputs (read before the wavefront overwrites u*)
     double x[KIN_NX];

@@ -813,6 +813,53 @@ int vc_debug_qp_fault(vc_ctx* c, int sqp_iter, int problem) {
   return 0;
 }
 
+int vc_debug_kin_merit(vc_ctx* c, int B, const void* x0, const void* kappa, const void* ds, const void* u_prev,
+                       void* u, const void* x_prev, void* x, int32_t* status, int32_t* iters, int32_t* st_acc,
+                       int32_t* it_acc, int first, int restart, void* u0, void* ls_diag, int flags) {
+  if (int r = check_common(c, B, flags)) return r;
+  if (c->model != VC_MODEL_KINEMATIC || c->dtype != VC_F64)
+    return fail(c, VC_E_UNSUPPORTED, "vc_debug_kin_merit: kinematic fp64 contexts only; model=%d dtype=%d", c->model,
+                c->dtype);
+  const bool ms = c->p.qp.ms != 0;
+  if (!x0 || !kappa || !ds || !u_prev || !u || !x || !status || !iters || !st_acc || !it_acc || !u0 || !ls_diag ||
+      (ms && !x_prev))
+    return fail(c, VC_E_ARG, "null pointer");
+  if (B == 0) return 0;
+  const int N = c->N, nx = 6, nu = 2;
+  const size_t u_bytes = (size_t)B * N * nu * 8, x_bytes = (size_t)B * (N + 1) * nx * 8;
+  vc::KinMeritArgs m{};
+  m.B = B;
+  m.N = N;
+  m.first = first != 0;
+  m.restart = restart != 0;
+  m.ms = ms;
+  m.L = c->p.kin_car.l;
+  m.w = c->p.kin_mpc;
+  m.obs = c->p.obs;
+  Staging st(c, flags);
+  if (int r = st.bind([&] {
+        m.x0 = st.in(x0, (size_t)B * nx * 8);
+        m.kappa = st.in(kappa, (size_t)B * N * 8);
+        m.ds = st.in(ds, (size_t)B * N * 8);
+        m.u_prev = st.in(u_prev, u_bytes);
+        m.ubar = st.inout(u, u_bytes);
+        // the state iterate is read under multiple shooting only (kin_solve alike); x_prev is then
+        // never dereferenced and stands on a valid buffer
+        m.x_out = st.pair(ms ? x : nullptr, x, x_bytes).wr;
+        m.x_prev = ms ? (const double*)st.in(x_prev, x_bytes) : (const double*)m.x_out;
+        // the QP's status / iteration count in, the step's out: one buffer each, as kin_solve aliases them
+        m.qp_status = m.status = st.inout(status, (size_t)B * 4);
+        m.qp_iters = m.iters = st.inout(iters, (size_t)B * 4);
+        m.st_acc = st.inout(st_acc, (size_t)B * 4);
+        m.it_acc = st.inout(it_acc, (size_t)B * 4);
+        m.u0 = st.out(u0, (size_t)B * nu * 8);
+        m.ls_diag = st.out(ls_diag, (size_t)B * 4 * 8);
+      }))
+    return r;
+  VC_HIP(c, vc::launch_kin_merit(m, c->stream));
+  return st.finish();
+}
+
 int vc_condense(vc_ctx* c, int B, const void* x0, const void* ubar, const void* kappa, const void* ds, void* H,
                 void* g, int flags) {
   if (int r = check_common(c, B, flags)) return r;

@@ -320,6 +320,30 @@ class Context:
                     M=dbg[:, n:n + n * n].reshape(B, n, n), Y=dbg[:, n + n * n:n + 2 * n * n].reshape(B, n, n),
                     rhs=dbg[:, n + 2 * n * n:2 * n + 2 * n * n], dz=dbg[:, 2 * n + 2 * n * n:3 * n + 2 * n * n])
 
+    def debug_kin_merit(self, x0, kappa, ds, u_prev, u, status, iters, st_acc, it_acc, first=True, restart=False,
+                        x_prev=None, x=None):
+        """``vc_debug_kin_merit`` (test hook, kinematic fp64): one launch of the merit line search
+        of the kinematic SQP step on its own.  ``u`` (the QP's u*), ``status`` / ``iters`` (the
+        QP's), ``st_acc`` / ``it_acc`` and, under ``vc_qp.ms``, ``x`` (the QP's x*) are overwritten
+        with the step's; ``x_prev`` is read under ``vc_qp.ms`` only.  Returns
+        (u0, x, u, status, iters, ls_diag[B, 4] = alpha, phi(u_prev), phi(accepted), D)."""
+        B, N, nx, f = self._batch(x0), self.N, self.nx, np.float64
+        ms = bool(self.params.qp.ms)
+        if ms and (x is None or x_prev is None):
+            raise ValueError("vc_qp.ms: pass the state iterate x_prev and the QP's x")
+        x = self._like(x0, (B, N + 1, nx)) if x is None else x
+        u0, diag = self._like(x0, (B, NU)), self._like(x0, (B, 4))
+        bufs = [x0, kappa, ds, u_prev, u] + ([x_prev] if ms else []) + [x, status, iters, st_acc, it_acc, u0, diag]
+        xs = [(B, N + 1, nx)]
+        shapes = [(B, nx), (B, N), (B, N), (B, N, NU), (B, N, NU)] + xs * ms + xs + [(B,)] * 4 + [(B, NU), (B, 4)]
+        dts = [f] * (6 + ms) + [np.int32] * 4 + [f, f]
+        p, flags = self._marshal(bufs, shapes, dts)
+        if not ms:
+            p.insert(5, C.c_void_p(0))
+        self._check(self.lib.vc_debug_kin_merit(self._h, B, *p[:11], int(bool(first)), int(bool(restart)), *p[11:],
+                                                flags))
+        return u0, x, u, status, iters, diag
+
     def rollout(self, x0, ubar, kappa, ds):
         B, N, nx, f = self._batch(x0), self.N, self.nx, _NP_DT[self.dtype]
         xbar = self._like(x0, (B, N + 1, nx))
