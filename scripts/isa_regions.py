@@ -10,7 +10,14 @@ instructions (s_* other than s_waitcnt / s_nop), the s_nop padding, and the vect
 other class names.  Counts are static: both arms of a uniform
 branch inside a region are in it, and a loop body counts once.
 
+With --blocks the input is the PRODUCTION build's assembly (no -DVC_TIMING: the timing build's
+register allocation differs) and the kernel's text is split at its basic-block labels instead, one
+row per block: its label, the source lines its .loc entries span (if the assembly has them), and
+the same classes.  The interior-point loop's blocks are the ones between the lines of its head and
+of the second Mehrotra pass's update; a block that a loop executes twice (the pass body) counts once.
+
 usage: python scripts/isa_regions.py kin_ltv_timing.s [min_instr]
+       python scripts/isa_regions.py --blocks kin_ltv.s [min_instr]
 """
 import re
 import sys
@@ -36,8 +43,10 @@ VECTOR = re.compile(r"^(v_|ds_|global_|flat_|buffer_|scratch_)")
 
 
 def main():
-    path = sys.argv[1]
-    min_instr = int(sys.argv[2]) if len(sys.argv) > 2 else 0
+    argv = [a for a in sys.argv[1:] if a != "--blocks"]
+    blocks = len(argv) != len(sys.argv) - 1
+    path = argv[0]
+    min_instr = int(argv[1]) if len(argv) > 1 else 0
     lines = open(path).read().split("\n")
     start = next(i for i, l in enumerate(lines) if re.match(r"^_ZN2vc14kin_ltv_kernel\w*:", l))
     end = next(i for i in range(start, len(lines)) if lines[i].startswith(".Lfunc_end"))
@@ -47,10 +56,18 @@ def main():
         m = re.match(r"\.loc\s+\d+\s+(\d+)", t)
         if m:
             loc = m.group(1)
+            if blocks and m.group(1) != "0":
+                cur["lo"] = min(cur.get("lo", 1 << 30), int(loc))
+                cur["hi"] = max(cur.get("hi", 0), int(loc))
+            continue
+        m = re.match(r"^(\.LBB\d+_\d+):", t)
+        if blocks and m:
+            regions.append(cur)
+            cur = {"open": m.group(1), "n": 0}
             continue
         if not t or t.startswith((";", ".", "//")) or t.endswith(":"):
             continue
-        if t.startswith("s_memtime"):
+        if not blocks and t.startswith("s_memtime"):
             regions.append(cur)
             cur = {"open": f"line {loc}", "n": 0}
             continue
@@ -63,14 +80,18 @@ def main():
         if not hit and VECTOR.match(t):
             cur["other vec"] = cur.get("other vec", 0) + 1
     regions.append(cur)
-    hdr = ["#", "opened at", "instr"] + [c for c, _ in CLASSES]
+    if blocks:
+        for r in regions:
+            r["open"] += f" (lines {r['lo']}-{r['hi']})" if "lo" in r else ""
+    hdr = ["#", "block" if blocks else "opened at", "instr"] + [c for c, _ in CLASSES]
     print("| " + " | ".join(hdr) + " |")
     print("|" + "---|" * len(hdr))
     for i, r in enumerate(regions):
         if r["n"] < min_instr:
             continue
         print("| " + " | ".join([str(i), r["open"], str(r["n"])] + [str(r.get(c, 0)) for c, _ in CLASSES]) + " |")
-    print(f"total instructions {sum(r['n'] for r in regions)}, stamps {len(regions) - 1}")
+    print(f"total instructions {sum(r['n'] for r in regions)}, {'blocks' if blocks else 'stamps'} "
+          f"{len(regions) - (0 if blocks else 1)}")
 
 
 if __name__ == "__main__":

@@ -10,7 +10,7 @@
 // Lane roles (n = 2N decision variables, NC = 2(N-1) state-constraint rows):
 //   lane j < n   owns decision variable dz_j: column j of the condensed
 //                sensitivity G during the forward sweep, row j of the normal
-//                matrix and of its Cholesky factor (registers Mr), and the two
+//                matrix and of its Cholesky factor (Mr while it is factored, then RowRegs), and the two
 //                box inequalities of u_j.
 //   lane r < NC  owns state-constraint row r: r < N-1 -> v_{r+1} >= v_min,
 //                else delta_{r-N+2} in [delta_min, delta_max].
@@ -23,7 +23,8 @@
 //
 // Register discipline (checked with `make resources`: no scratch): Mr[n] is the
 // only register array in the solver loops and is indexed with compile-time
-// indices only (fully unrolled loops); lane-dependent stores are branch-free
+// indices only (fully unrolled loops); between a factorisation and the solves the
+// row waits in accumulator registers (RowRegs); lane-dependent stores are branch-free
 // (dummy LDS slots) because divergent ifs inside the unrolled factorisation make
 // the register allocator spill; sched_barrier fences bound how far the
 // scheduler hoists LDS broadcast reads; LDS is static so every address folds
@@ -391,11 +392,88 @@ template <int N>
 __device__ __forceinline__ void store_rows(const double (&Mr)[Dims<N>::n], Smem<N>& s, int lane) {
 }
 
-// Solve (L L') x = b, lane j holding b_j; returns x_j.  Forward sweep: y_k = acc_k / L_kk is
-// broadcast from lane k, and every lane subtracts L[lane][k] y_k from its accumulator with the
-// row registers zero on and above the diagonal (factor_blocked), so lane k's accumulator stops
-// changing once y_k is taken and y = acc / L_kk at the end -- no per-step select (a finite
-// factor times 0 subtracts exactly 0: the same values as collecting y_k per step).  Backward
+// Row `lane` of the Cholesky factor between a factorisation and the solves that use it, held in
+// accumulator registers (two 32-bit halves per entry): VALU instructions cannot address AGPRs, so
+// the 80 registers of the row stay out of the vector file while the Mehrotra passes, the residuals
+// and the polish run, and an entry reaches a VGPR only where an instruction needs it.
+template <int N>
+struct RowRegs {
+  int lo[Dims<N>::n], hi[Dims<N>::n];
+};
+// R[k] = v on every lane.  Lane j's entries k >= j are whatever the factorisation left on and above
+// the diagonal (finite, meaningless): the forward sweep never lets them act (see there), so the row
+// is not zeroed.
+template <int N>
+__device__ __forceinline__ void row_put(RowRegs<N>& R, int k, double v) {
+  asm("v_accvgpr_write_b32 %0, %1" : "=a"(R.lo[k]) : "v"(__double2loint(v)));
+  asm("v_accvgpr_write_b32 %0, %1" : "=a"(R.hi[k]) : "v"(__double2hiint(v)));
+}
+// acc -= L[lane][k] * (acc * dj of lane k) on lanes > k, for k = 0..n-1: the forward sweep of the
+// triangular solves, as ONE asm statement of n steps.
+//   - Lane j's accumulator stops changing once y_j is taken (row j has no entry at or beyond the
+//     diagonal).  The sweep gets that from EXEC, not from zeros in the row: step k's fma runs on lanes
+//     k+1..63 (one s_bfm_b64 per step; v_readlane ignores EXEC, and the next step's product is needed
+//     from lane k+1 on, which is the same set).  So the factorisation does not zero its row registers
+//     on and above the diagonal -- 40 masks and 80 selects per factorisation.
+//     A finite L times 0 subtracted exactly 0, so the values are the ones the zeroed row gave.
+//   - gfx950 wants one wait state between the v_mul_f64 and the v_readlane that reads its result, and
+//     two between the second v_readlane and the v_fma_f64 that reads the SGPR pair.  The s_bfm_b64
+//     stands in the first (right before the fma it cost 12 cycles a step: the VALU waits for a fresh
+//     EXEC), the two v_accvgpr_read that bring the step's row entry into the vector file in the other
+//     two, so the entry lives in VGPRs for one step.
+//   - The product and the entry sit in fixed registers (an asm operand cannot name the halves of a
+//     64-bit register), the broadcast in VCC, the caller's EXEC in s[98:99]: all clobbered, EXEC
+//     restored.  The kernel's one wave is full (64 threads, uniform control flow).
+//   - One statement, not one per step: the compiler cannot see into an asm statement and pads every
+//     read of a register the previous statement wrote with an s_nop of its own.
+// The arithmetic is what the compiler made of  acc -= Lr[k] * lane_bcast(acc * dj, k):  one rounded
+// product, one fma.
+#define KIN_FS_STEP(k, w, lo)                    \
+  "v_mul_f64 v[252:253], %[acc], %[dj]\n\t"      \
+  "s_bfm_b64 exec, " #w ", " #lo "\n\t"          \
+  "v_readlane_b32 vcc_lo, v252, " #k "\n\t"      \
+  "v_readlane_b32 vcc_hi, v253, " #k "\n\t"      \
+  "v_accvgpr_read_b32 v254, %[l" #k "]\n\t"      \
+  "v_accvgpr_read_b32 v255, %[h" #k "]\n\t"      \
+  "v_fma_f64 %[acc], -v[254:255], vcc, %[acc]\n\t"
+#define KIN_FS_ROW(k) [l##k] "a"(Lr.lo[k]), [h##k] "a"(Lr.hi[k])
+template <int N>
+__device__ __forceinline__ void forward_sweep(const RowRegs<N>& Lr, double& acc, double dj) {
+  static_assert(Dims<N>::n == 40, "the sweep's 40 steps are written out");
+  asm("s_mov_b64 s[98:99], exec\n\t"
+      KIN_FS_STEP(0,63,1) KIN_FS_STEP(1,62,2) KIN_FS_STEP(2,61,3)
+      KIN_FS_STEP(3,60,4) KIN_FS_STEP(4,59,5) KIN_FS_STEP(5,58,6)
+      KIN_FS_STEP(6,57,7) KIN_FS_STEP(7,56,8) KIN_FS_STEP(8,55,9)
+      KIN_FS_STEP(9,54,10) KIN_FS_STEP(10,53,11) KIN_FS_STEP(11,52,12)
+      KIN_FS_STEP(12,51,13) KIN_FS_STEP(13,50,14) KIN_FS_STEP(14,49,15)
+      KIN_FS_STEP(15,48,16) KIN_FS_STEP(16,47,17) KIN_FS_STEP(17,46,18)
+      KIN_FS_STEP(18,45,19) KIN_FS_STEP(19,44,20) KIN_FS_STEP(20,43,21)
+      KIN_FS_STEP(21,42,22) KIN_FS_STEP(22,41,23) KIN_FS_STEP(23,40,24)
+      KIN_FS_STEP(24,39,25) KIN_FS_STEP(25,38,26) KIN_FS_STEP(26,37,27)
+      KIN_FS_STEP(27,36,28) KIN_FS_STEP(28,35,29) KIN_FS_STEP(29,34,30)
+      KIN_FS_STEP(30,33,31) KIN_FS_STEP(31,32,32) KIN_FS_STEP(32,31,33)
+      KIN_FS_STEP(33,30,34) KIN_FS_STEP(34,29,35) KIN_FS_STEP(35,28,36)
+      KIN_FS_STEP(36,27,37) KIN_FS_STEP(37,26,38) KIN_FS_STEP(38,25,39)
+      KIN_FS_STEP(39,24,40)
+      "s_mov_b64 exec, s[98:99]"
+      : [acc] "+v"(acc)
+      : [dj] "v"(dj),
+        KIN_FS_ROW(0), KIN_FS_ROW(1), KIN_FS_ROW(2), KIN_FS_ROW(3), KIN_FS_ROW(4), KIN_FS_ROW(5),
+        KIN_FS_ROW(6), KIN_FS_ROW(7), KIN_FS_ROW(8), KIN_FS_ROW(9), KIN_FS_ROW(10), KIN_FS_ROW(11),
+        KIN_FS_ROW(12), KIN_FS_ROW(13), KIN_FS_ROW(14), KIN_FS_ROW(15), KIN_FS_ROW(16), KIN_FS_ROW(17),
+        KIN_FS_ROW(18), KIN_FS_ROW(19), KIN_FS_ROW(20), KIN_FS_ROW(21), KIN_FS_ROW(22), KIN_FS_ROW(23),
+        KIN_FS_ROW(24), KIN_FS_ROW(25), KIN_FS_ROW(26), KIN_FS_ROW(27), KIN_FS_ROW(28), KIN_FS_ROW(29),
+        KIN_FS_ROW(30), KIN_FS_ROW(31), KIN_FS_ROW(32), KIN_FS_ROW(33), KIN_FS_ROW(34), KIN_FS_ROW(35),
+        KIN_FS_ROW(36), KIN_FS_ROW(37), KIN_FS_ROW(38), KIN_FS_ROW(39)
+      : "vcc", "s98", "s99", "v252", "v253", "v254", "v255");
+}
+#undef KIN_FS_STEP
+#undef KIN_FS_ROW
+
+// Solve (L L') x = b, lane j holding b_j; returns x_j.  Forward sweep (forward_sweep): y_k =
+// acc_k / L_kk is broadcast from lane k, and the lanes below subtract L[lane][k] y_k from their
+// accumulators, so lane k's accumulator stops changing once y_k is taken and y = acc / L_kk at
+// the end -- no per-step select.  Backward
 // sweep: lane i reads L[k][i] (row k of the packed rows, store_rows; or column i of the factor)
 // from LDS at immediate offsets of one per-lane base, prefetched one 8-step chunk ahead, and x_i
 // is written into lane i at step i by v_writelane (entries k <= i of the read are other rows'
@@ -403,7 +481,7 @@ __device__ __forceinline__ void store_rows(const double (&Mr)[Dims<N>::n], Smem<
 // per element.  (A four-unknown blocked variant
 // was 13 % slower: the sweeps are bound by instruction issue, profiles/r03/section_cycles_r03g.txt.)
 template <int N>
-__device__ double chol_solve(const double (&Lr)[Dims<N>::n], const Smem<N>& s, double b, int lane) {
+__device__ double chol_solve(const RowRegs<N>& Lr, const Smem<N>& s, double b, int lane) {
   constexpr int n = Dims<N>::n;
   constexpr int CH = KIN_SOLVE_CH;
   static_assert(n % CH == 0, "backward prefetch chunks");
@@ -411,9 +489,8 @@ __device__ double chol_solve(const double (&Lr)[Dims<N>::n], const Smem<N>& s, d
   lds_cdouble* col = lds_opaque(&s.Lc[lc_base<n>(row)]);  // col[k] = L[k][row] for k > row
   const double dj = s.dinv[row];
   double acc = b;
-#pragma unroll
-  for (int k = 0; k < n; ++k) acc -= Lr[k] * lane_bcast(acc * dj, k);  // L y = b
-  acc *= dj;                                                           // y
+  forward_sweep<N>(Lr, acc, dj);  // L y = b
+  acc *= dj;                      // y
   double x = 0.0;
   double lk[2][CH];
   lds_cdouble* zero = lds_opaque(&s.zrow[0]);
@@ -610,8 +687,9 @@ __device__ __forceinline__ void build_normal_mfma(double (&Mr)[Dims<N>::n], Smem
 // (I, J) with p < J <= I, take the panel's rank-16 update on the matrix cores
 // (v_mfma_f64_16x16x4_f64, operands = the just-stored factor columns from LDS): the trailing
 // update, 880 VALU FMAs + 380 broadcast reads in the row-per-lane factorisation, becomes
-// 16 MFMAs.  Output: s.Lc columns, s.dinv (inverse pivots), Mr = row `lane` of L strictly
-// below the diagonal.  Buffers and what each aliases: panel 0's three tiles lie in s.Lc from its
+// 16 MFMAs.  Output: s.Lc columns, s.dinv (inverse pivots), Lr = row `lane` of L strictly
+// below the diagonal (accumulator registers; entries on and above it are not meaningful).
+// Buffers and what each aliases: panel 0's three tiles lie in s.Lc from its
 // start (720 doubles: no column of this factor is stored yet, and the previous factor's last
 // readers -- the solves, factor_update -- were issued before, LDS executing a wave's operations
 // in order); panel 1's tile (1,1) lies in the storage of columns >= 16 (written only by panel 1's
@@ -631,8 +709,9 @@ __device__ __forceinline__ void build_normal_mfma(double (&Mr)[Dims<N>::n], Smem
 // second pivot from the block's determinant, both rsq chains in parallel, measured no gain in
 // round 6: the steps are bound by issue, not by the pivot chain.)
 template <int N>
-__device__ bool factor_blocked(double (&Mr)[Dims<N>::n], d4 (&acc)[Tiles<N>::NT], Smem<N>& s, int lane) {
+__device__ bool factor_blocked(RowRegs<N>& Lr, d4 (&acc)[Tiles<N>::NT], Smem<N>& s, int lane) {
   constexpr int n = Dims<N>::n, NB = Tiles<N>::NB;
+  double Mr[n];  // this lane's row while it is factored; it leaves in Lr
   constexpr int DUMMY = Smem<N>::LC_DUMMY;
   static_assert(NB == 3 && n > 32 && n <= 40, "three panels, the last one at most 8 wide");
   static_assert(lc_start<n>(16) + 16 * 18 <= DUMMY, "panel 0/1 transpose buffer inside the factor storage");
@@ -814,15 +893,10 @@ __device__ bool factor_blocked(double (&Mr)[Dims<N>::n], d4 (&acc)[Tiles<N>::NT]
       }
     }
   }
-  // the row registers zero on and above the diagonal (what the solves' forward sweeps rely on), in
-  // one pass once every column's update has read its unmasked value.  Written inside the pivot
-  // steps, the compiler computed the 40 compares there, kept the masks alive to the selects it sank
-  // down here anyway, and spilled 18 mask pairs through VGPR lanes on the way.  The lane is
-  // laundered per column: with one opaque lane for the whole pass the kernel spills 20 bytes per
-  // lane to scratch.
+  // the row to the accumulator registers as it is: the forward sweep masks what lies on and above
+  // the diagonal (the zeroing pass that stood here was 246 instructions per factorisation)
 #pragma unroll
-  for (int k = 0; k < n; ++k) Mr[k] = lane_opaque(lane) > k ? Mr[k] : 0.0;
-  store_rows<N>(Mr, s, lane);
+  for (int k = 0; k < n; ++k) row_put<N>(Lr, k, Mr[k]);
   wave_sync();  // factor and inverse pivots visible to the solves
   return ok;
 }
@@ -857,9 +931,10 @@ __device__ __forceinline__ double wave_prefix(double v, int lane) {
 // w is zeroed at column k, so the entries on and above the diagonal stay 0.  (numpy check of both
 // cases against a fresh Cholesky: <= 9e-15 relative.)
 template <int N>
-__device__ bool factor_update(double (&Mr)[Dims<N>::n], Smem<N>& s, int upd, int j, bool fixed, double sqrho,
+__device__ bool factor_update(RowRegs<N>& Lr, Smem<N>& s, int upd, int j, bool fixed, double sqrho,
                               int lane) {
   constexpr int n = Dims<N>::n;
+  double Mr[n];
   constexpr int DUMMY = Smem<N>::LC_DUMMY, ZERO = Smem<N>::LC_ZERO;
   lane = lane_opaque(lane);
   const int row = lane < n ? lane : 0;
@@ -877,17 +952,19 @@ __device__ bool factor_update(double (&Mr)[Dims<N>::n], Smem<N>& s, int upd, int
     z = (lane < n && !fixed) ? sqrho * s.G[j][lane < n ? lane : n] : 0.0;
   }
   wave_sync();
-  // the rows from the stored columns (Mr is dead between rounds: the KKT check needs its registers)
+  // the rows from the stored columns: into the accumulator registers for the forward sweep, and kept
+  // in Mr for the column sweep below
   {
     lds_cdouble* L = lds_opaque(&s.Lc[0]);
 #pragma unroll
     for (int k = 0; k < n; ++k) Mr[k] = L[below(k, ZERO)];
   }
+#pragma unroll
+  for (int k = 0; k < n; ++k) row_put<N>(Lr, k, Mr[k]);
   // y = L^-1 z (chol_solve's forward sweep)
   const double dj = s.dinv[row];
   double acc = z;
-#pragma unroll
-  for (int k = 0; k < n; ++k) acc -= Mr[k] * lane_bcast(acc * dj, k);
+  forward_sweep<N>(Lr, acc, dj);
   const double y = lane < n ? acc * dj : 0.0;
   const double t = 1.0 + wave_prefix(y * y, lane);
   const double sk = sqrt(t / (t - y * y)), ck = y / t;
@@ -916,6 +993,8 @@ __device__ bool factor_update(double (&Mr)[Dims<N>::n], Smem<N>& s, int upd, int
   }
 #pragma unroll
   for (int k = 0; k < n - 1; ++k) s.Lc[below(k, DUMMY)] = Mr[k];
+#pragma unroll
+  for (int k = 0; k < n; ++k) row_put<N>(Lr, k, Mr[k]);
   wave_sync();  // factor and inverse pivots visible to the solves
   return ok;
 }
@@ -1227,7 +1306,7 @@ __global__ __launch_bounds__(64) void kin_ltv_kernel(KinLtvArgs A) {
   int it = 0;
   bool converged = false, chol_fail = false, near = false;
   double last_res = 0.0, last_mu = 0.0;
-  double Mr[n];
+  RowRegs<N> Mr;  // row `lane` of the current factor (accumulator registers)
   // Residuals: dual rd = H z + g + C' lambda (lane j < n), primal r = C z + s - d per row side.
   // Computed once at the start point and then carried by the step -- the
   // direction solves the linearised KKT system, whose dual and primal rows are linear, so a step
