@@ -448,6 +448,17 @@ int vc_debug_sqp_breakdown(vc_ctx* ctx, int sqp_iter, int problem, int levels);
  * No reference counterpart. */
 int vc_debug_rcp(vc_ctx* ctx, int n, const void* x, void* out, int flags);
 
+/* Test diagnostics (kinematic fp64 contexts, N = 20): the fused kernel's two products with the
+ * condensed constraint matrix, evaluated by the device functions the solver calls (csrc/kin_ltv.hip
+ * grow_dot, gt_dot) on operands given here, B (<= max_batch) independent sets: G[B][2(N-1)][2N],
+ * vz[B][2N], vc[B][2(N-1)] fp64.  out_grow[B][64] = G vz (row r in lane r), out_gt[B][64] = G' vc
+ * (column j in lane j), all 64 lanes of the wave as the functions return them (+0 in the lanes that
+ * own no row / column).  The products skip the entries of G that the condensing leaves structurally
+ * zero (row r of stage k = r + 1 or r - N + 2: columns >= 2k), whatever the caller puts there.
+ * No reference counterpart. */
+int vc_debug_kin_gdots(vc_ctx* ctx, int B, const void* G, const void* vz, const void* vc, void* out_grow,
+                       void* out_gt, int flags);
+
 /* Predict: xbar[B][N+1][nx] from x0[B][nx] and ubar[B][N][nu] (spatial step). */
 int vc_rollout(vc_ctx* ctx, int B, const void* x0, const void* ubar, const void* kappa,
                const void* ds, void* xbar, int flags);

@@ -314,22 +314,144 @@ __device__ __forceinline__ double lds_dot(lds_cdouble* a, lds_cdouble* b) {
   return a0 + a1;
 }
 
-// y_r = G_r . v for lane r (v broadcast in s.vz); rows have <= 2(N-1) nonzeros
+// ---- the two G products, split by parity over the idle lanes ---------------------------------------
+// lds_dot sums 38 terms as two chains, a0 over the even indices and a1 over the odd ones, ascending,
+// every term an fma and the first one onto +0, and returns a0 + a1.  Row r of G (stage k =
+// crow_stage(r)) is exactly zero from column 2k on, so on average half of those fmas are
+// fma(+-0, v, acc), which is acc whenever v is finite (acc is never -0: each chain starts from
+// x y + (+0)) -- and a lane-uniform loop cannot skip them while 24 to 26 lanes of the wave idle.
+// Here every lane runs ONE accumulator through the same 19 steps; step t reads index 2t plus a shift
+// of its lane, at immediate offsets from per-lane bases:
+//   - a LONG row / column (its nonzeros span the whole index range) runs its even chain in its own
+//     lane and its odd chain in a partner lane among the idle ones; one cross-lane fetch and the add
+//     a0 + a1 join them;
+//   - a SHORT one (nonzeros within half the range) runs its even chain in steps 0..9 and its odd chain
+//     in steps 10..18: at step 10 every lane stashes its accumulator and the short lanes restart from
+//     +0; the result is stash + acc.
+// The chains are the parent's chains without terms whose G factor is an exact zero, the roundings are
+// the same, so is every result bit -- PROVIDED the dropped G entries are exact zeros and v is finite
+// (fma(0, inf or NaN, acc) is NaN, and the row / column would have been NaN in the 38-term form).  The
+// sweep writes those entries as c + h a (J . 0) with c = +0, exact zeros while the stage Jacobians
+// are finite; a non-finite Jacobian of stage k makes dq NaN in every column, column 0 included, so
+// such a row is NaN in both forms.  v: see the call sites.
+// Operands of the 19 steps are loaded one segment (5, 5, 4, 5 steps) ahead of their fmas.
 template <int N>
-__device__ double grow_dot(const Smem<N>& s, int lane) {
-  constexpr int NC = Dims<N>::NC;
-  const int r = lane < NC ? lane : 0;
-  const double a = lds_dot<2 * (N - 1), 1, 1>(lds_opaque(&s.G[r][0]), lds_opaque(&s.vz[0]));
-  return lane < NC ? a : 0.0;
+struct GSplit {
+  static_assert(N == 20, "the lane plan below is worked out for N = 20 (the one instantiation)");
+  static constexpr int NC = Dims<N>::NC, n = Dims<N>::n, LD = Dims<N>::LD;
+  static constexpr int T = NC / 2;  // steps of a parity chain
+  // grow_dot.  Short rows: stage <= 9 (nonzero columns < 18), r = 0..8 and N-1..N+7; long rows
+  // r = 9..18 and 28..37, partner lanes NC..NC+19 (NC + r - 9 and NC + r - 18)
+  static constexpr int ROW_SHORT = T - (T + 1) / 2;  // 9
+  static_assert(NC + 2 * (N - 1 - ROW_SHORT) <= 64, "partner lanes of the long rows");
+  // gt_dot.  Column j is nonzero at rows r >= j/2 (v rows) and r >= j/2 + N (delta rows): long
+  // columns j < 20, partner lanes n..n+19; short columns j >= 20 read the rows 10..18 | 28..36 |
+  // 11..17 | 29..37, shifts +10, +18, -9, +1 against the long lanes' row 2t in the four segments
+  static constexpr int COL_LONG = n / 2;
+  static_assert(n + COL_LONG <= 64, "partner lanes of the long columns");
+};
+
+// value of `v` in the lane whose index times four is `byte_lane` (any lane may ask for any lane)
+__device__ __forceinline__ double lane_fetch(double v, int byte_lane) {
+  const int lo = __builtin_amdgcn_ds_bpermute(byte_lane, __double2loint(v));
+  const int hi = __builtin_amdgcn_ds_bpermute(byte_lane, __double2hiint(v));
+  return __hiloint2double(hi, lo);
 }
 
-// (G' v)_j for lane j (v broadcast in s.vc)
+// steps T0..T1-1 of a chain: operands G[(2 t - D) GS], v[2 t - D] from this lane's segment bases
+// (D <= 2 T0: no lane's base lies below the arrays, whatever their LDS address)
+template <int T0, int T1, int GS, int D>
+__device__ __forceinline__ void gsplit_fetch(double (&a)[5], double (&b)[5], uint32_t g, uint32_t v) {
+  static_assert(2 * T0 - D >= 0, "offsets from a segment base are not negative");
+  lds_cdouble* gp = (lds_cdouble*)(uintptr_t)g;
+  lds_cdouble* vp = (lds_cdouble*)(uintptr_t)v;
+#pragma unroll
+  for (int t = T0; t < T1; ++t) {
+    a[t - T0] = gp[(2 * t - D) * GS];
+    b[t - T0] = vp[2 * t - D];
+  }
+}
+template <int CNT>
+__device__ __forceinline__ double gsplit_fma(const double (&a)[5], const double (&b)[5], double acc) {
+#pragma unroll
+  for (int q = 0; q < CNT; ++q) acc = __builtin_fma(a[q], b[q], acc);
+  return acc;
+}
+// the 19 steps; g[k], v[k]: byte addresses segment k's operands are read from, step t at index 2t - D
+// (D2, D3 for segments 2, 3; 0 for the first two) -- the lane's shift is in the address.
+// Returns the lane's accumulator and, in `stash`, its value before step 10 (short lanes: the even chain)
+template <int N, int GS, int D2, int D3>
+__device__ __forceinline__ double gsplit_chain(const uint32_t (&g)[4], const uint32_t (&v)[4], bool shrt,
+                                               double& stash) {
+  static_assert(GSplit<N>::T == 19, "segments of 5, 5, 4 and 5 steps");
+  double a0[5], b0[5], a1[5], b1[5];
+  gsplit_fetch<0, 5, GS, 0>(a0, b0, g[0], v[0]);
+  gsplit_fetch<5, 10, GS, 0>(a1, b1, g[1], v[1]);
+  fence();
+  double acc = gsplit_fma<5>(a0, b0, 0.0);
+  gsplit_fetch<10, 14, GS, D2>(a0, b0, g[2], v[2]);
+  fence();
+  acc = gsplit_fma<5>(a1, b1, acc);
+  gsplit_fetch<14, 19, GS, D3>(a1, b1, g[3], v[3]);
+  fence();
+  stash = acc;
+  acc = shrt ? 0.0 : acc;
+  acc = gsplit_fma<4>(a0, b0, acc);
+  fence();
+  acc = gsplit_fma<5>(a1, b1, acc);
+  fence();
+  return acc;
+}
+
+// y_r = G_r . v for lane r (v broadcast in s.vz), 0 in lanes >= NC.  Every lane of the wave must call it
+// (the long rows' odd chains run in lanes NC..NC+19).  Reads G[r][0..37], vz[0..37] as the 38-term form.
+template <int N>
+__device__ double grow_dot(const Smem<N>& s, int lane) {
+  using P = GSplit<N>;
+  constexpr int NC = P::NC, LD = P::LD;
+  const int l = lane_opaque(lane);  // the bases are recomputed here, not hoisted out of the loops
+  const bool part = l >= NC;
+  const bool shrt = uint32_t(l) < uint32_t(P::ROW_SHORT) || uint32_t(l - (N - 1)) < uint32_t(P::ROW_SHORT);
+  // partner lane NC + q: row q + 9 (q < 10), q + 18 (q < 20), the zero row NC beyond
+  const int r = min(part ? l - (l < NC + (N - 1 - P::ROW_SHORT) ? NC - P::ROW_SHORT : N) : l, NC);
+  const uint32_t odd = part ? 8u : 0u;                      // partners start at index 1
+  const uint32_t fwd = shrt ? 0u : 8u * uint32_t(P::T);     // steps >= 10 read index 2t - 19 + this: short rows 1, 3, ..
+  const uint32_t g0 = (uint32_t)(uintptr_t)(lds_cdouble*)&s.G[0][0] + uint32_t(r) * (8u * LD) + odd;
+  const uint32_t v0 = (uint32_t)(uintptr_t)(lds_cdouble*)&s.vz[0] + odd;
+  const uint32_t g[4] = {g0, g0, g0 + fwd, g0 + fwd}, v[4] = {v0, v0, v0 + fwd, v0 + fwd};
+  double stash;
+  const double acc = gsplit_chain<N, 1, P::T, P::T>(g, v, shrt, stash);
+  const double other = lane_fetch(acc, 4 * (l + (l < N - 1 ? NC - P::ROW_SHORT : N)));  // long row: its partner
+  const double y = acc + (shrt ? stash : other);
+  return l < NC ? y : 0.0;
+}
+
+// (G' v)_j for lane j (v broadcast in s.vc), 0 in lanes >= n.  Every lane of the wave must call it (the
+// long columns' odd chains run in lanes n..n+19).  Reads rows 0..37 of G and vc[0..37] as the 38-term form.
 template <int N>
 __device__ double gt_dot(const Smem<N>& s, int lane) {
-  constexpr int n = Dims<N>::n, NC = Dims<N>::NC, LD = Dims<N>::LD;
-  const int j = lane < n ? lane : 0;
-  const double a = lds_dot<NC, LD, 1>(lds_opaque(&s.G[0][j]), lds_opaque(&s.vc[0]));
-  return lane < n ? a : 0.0;
+  using P = GSplit<N>;
+  constexpr int n = P::n, LD = P::LD;
+  const int l = lane_opaque(lane);
+  const bool part = l >= n;
+  const bool shrt = uint32_t(l - P::COL_LONG) < uint32_t(n - P::COL_LONG);
+  const int j = part ? l - n : l;  // lanes n+20.. repeat columns 20..23 (discarded)
+  const uint32_t ms = shrt ? 1u : 0u, mp = part ? 1u : 0u;
+  const uint32_t gp = (uint32_t)(uintptr_t)(lds_cdouble*)&s.G[0][0] + uint32_t(j) * 8u + mp * (8u * LD);
+  const uint32_t vp = (uint32_t)(uintptr_t)(lds_cdouble*)&s.vc[0] + mp * 8u;
+  // rows read in segment k: 2t - D[k] + (short columns SH[k], long ones D[k], partners D[k] + 1)
+  constexpr int SH[4] = {10, 18, 0, 1}, D[4] = {0, 0, 9, 0};
+  uint32_t g[4], v[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    g[k] = gp + uint32_t(D[k] * 8 * LD) + ms * uint32_t((SH[k] - D[k]) * 8 * LD);
+    v[k] = vp + uint32_t(D[k] * 8) + ms * uint32_t((SH[k] - D[k]) * 8);
+  }
+  double stash;
+  const double acc = gsplit_chain<N, LD, D[2], D[3]>(g, v, shrt, stash);
+  const double other = lane_fetch(acc, 4 * (l + n));  // long column j: lane n + j
+  const double y = acc + (shrt ? stash : other);
+  return l < n ? y : 0.0;
 }
 
 
@@ -1326,13 +1448,13 @@ __global__ __launch_bounds__(64) void kin_ltv_kernel(KinLtvArgs A) {
     s.vc[lane] = (lane < NC) ? (cs.lhi - cs.llo) : 0.0;
     wave_sync();
     const double yc = grow_dot<N>(s, lane);
-    // H z outside the select's branch, every lane taking part (lanes >= n repeat row 0), G' lambda
-    // inside it: with both inside, the allocator kept two of the loop's values in scratch across
-    // them; with both outside, hundreds of bytes
+    // H z and G' lambda outside the select, every lane taking part (lanes >= n repeat row 0 of H
+    // and run the long columns' odd chains of G')
     fence();
     const double hz = h_dot<N>(s, lane);
     fence();
-    rd = (lane < n) ? (hz + gj + (bx.lhi - bx.llo) + gt_dot<N>(s, lane)) : 0.0;
+    const double gtl = gt_dot<N>(s, lane);
+    rd = (lane < n) ? (hz + gj + (bx.lhi - bx.llo) + gtl) : 0.0;
     rlo_b = bx.hasLo ? (z - bx.lo - bx.slo) : 0.0;
     rhi_b = bx.hasHi ? (bx.hi - z - bx.shi) : 0.0;
     rlo_c = cs.hasLo ? (yc - cs.lo - cs.slo) : 0.0;
@@ -1438,7 +1560,8 @@ __global__ __launch_bounds__(64) void kin_ltv_kernel(KinLtvArgs A) {
         wave_sync();
         s.vc[lane] = (lane < NC) ? ec : 0.0;
         wave_sync();
-        const double rhs = (lane < n) ? (-rd - eb - gt_dot<N>(s, lane)) : 0.0;
+        const double gte = gt_dot<N>(s, lane);  // every lane: the partner lanes' chains
+        const double rhs = (lane < n) ? (-rd - eb - gte) : 0.0;
         VC_TSTAMP(t_sol0)
         const double dz = chol_solve<N>(Mr, s, rhs, lane);
         VC_TACC(T_SOLVE, t_sol0)
@@ -1639,7 +1762,8 @@ __global__ __launch_bounds__(64) void kin_ltv_kernel(KinLtvArgs A) {
         wave_sync();
         s.vc[lane] = (lane < NC) ? (nu_c - rho_c * bnd_c) : 0.0;
         wave_sync();
-        const double rhs = (lane < n) ? (fixed ? zfix : (base - gt_dot<N>(s, lane))) : 0.0;
+        const double gtn = gt_dot<N>(s, lane);
+        const double rhs = (lane < n) ? (fixed ? zfix : (base - gtn)) : 0.0;
         zp = chol_solve<N>(Mr, s, rhs, lane);
         wave_sync();
         s.vz[lane] = (lane < n) ? zp : 0.0;
@@ -1694,7 +1818,8 @@ __global__ __launch_bounds__(64) void kin_ltv_kernel(KinLtvArgs A) {
       s.vz[lane] = (lane < n) ? zp : 0.0;
       s.vc[lane] = (lane < NC) ? nu_c : 0.0;
       wave_sync();
-      const double grad = (lane < n) ? (h_dot<N>(s, lane) + gj + gt_dot<N>(s, lane)) : 0.0;
+      const double gtnu = gt_dot<N>(s, lane);
+      const double grad = (lane < n) ? (h_dot<N>(s, lane) + gj + gtnu) : 0.0;
       const double ypc = grow_dot<N>(s, lane);
       // the true violation, not CG's recurrence -- and, with KIN_STAT_CHECK, the free variables'
       // stationarity (the solves are trusted to make it ~0; a factor gone inaccurate must not certify)
@@ -1875,7 +2000,35 @@ __global__ __launch_bounds__(64) void kin_ltv_kernel(KinLtvArgs A) {
 #endif
 }
 
+// Test hook (vc_debug_kin_gdots): grow_dot and gt_dot as the solver calls them, on operands the caller
+// gives -- G[B][NC][n], vz[B][n], vc[B][NC] -- all 64 lanes of each result to out_grow / out_gt[B][64]
+template <int N>
+__global__ __launch_bounds__(64) void kin_gdots_kernel(int B, const double* G, const double* vz, const double* vc,
+                                                       double* out_grow, double* out_gt) {
+  constexpr int n = Dims<N>::n, NC = Dims<N>::NC, LD = Dims<N>::LD;
+  __shared__ Smem<N> s;
+  const int lane = threadIdx.x;
+  const int b = blockIdx.x;
+  if (b >= B) return;
+  for (int i = lane; i < (NC + 3) * LD; i += 64) (&s.G[0][0])[i] = 0.0;  // padding column, rows NC..NC+2
+  wave_sync();
+  for (int i = lane; i < NC * n; i += 64) s.G[i / n][i % n] = G[(size_t)b * NC * n + i];
+  s.vz[lane] = lane < n ? vz[(size_t)b * n + lane] : 0.0;
+  s.vc[lane] = lane < NC ? vc[(size_t)b * NC + lane] : 0.0;
+  wave_sync();
+  out_grow[(size_t)b * 64 + lane] = grow_dot<N>(s, lane);
+  out_gt[(size_t)b * 64 + lane] = gt_dot<N>(s, lane);
+}
+
 // ---- host launcher ---------------------------------------------------------------
+hipError_t launch_kin_gdots(int B, int N, const double* G, const double* vz, const double* vc, double* out_grow,
+                            double* out_gt, hipStream_t stream) {
+  if (B <= 0) return hipSuccess;
+  if (N != 20) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(kin_gdots_kernel<20>, dim3(B), dim3(64), 0, stream, B, G, vz, vc, out_grow, out_gt);
+  return hipGetLastError();
+}
+
 size_t kin_ltv_smem_bytes(int N) {
   switch (N) {
     case 20: return sizeof(Smem<20>);

@@ -806,6 +806,28 @@ int vc_debug_rcp(vc_ctx* c, int n, const void* x, void* out, int flags) {
   return st.finish();
 }
 
+int vc_debug_kin_gdots(vc_ctx* c, int B, const void* G, const void* vz, const void* vc, void* out_grow,
+                       void* out_gt, int flags) {
+  if (int r = check_common(c, B, flags)) return r;
+  if (c->model != VC_MODEL_KINEMATIC || c->dtype != VC_F64 || vc::kin_ltv_smem_bytes(c->N) == 0)
+    return fail(c, VC_E_UNSUPPORTED, "vc_debug_kin_gdots: kinematic fp64 contexts with the fused kernel's N only");
+  if (!G || !vz || !vc || !out_grow || !out_gt) return fail(c, VC_E_ARG, "null pointer");
+  if (B == 0) return 0;
+  const int N = c->N, n = 2 * N, NC = 2 * (N - 1);
+  Ptr dG, dvz, dvc, dgrow, dgt;
+  Staging st(c, flags);
+  if (int r = st.bind([&] {
+        dG = st.in(G, (size_t)B * NC * n * 8);
+        dvz = st.in(vz, (size_t)B * n * 8);
+        dvc = st.in(vc, (size_t)B * NC * 8);
+        dgrow = st.out(out_grow, (size_t)B * 64 * 8);
+        dgt = st.out(out_gt, (size_t)B * 64 * 8);
+      }))
+    return r;
+  VC_HIP(c, vc::launch_kin_gdots(B, N, dG, dvz, dvc, dgrow, dgt, c->stream));
+  return st.finish();
+}
+
 int vc_debug_qp_fault(vc_ctx* c, int sqp_iter, int problem) {
   if (!c) return VC_E_ARG;
   c->fault_iter = sqp_iter;
