@@ -79,7 +79,8 @@ enum vc_tyre { VC_TYRE_FIALA = 0, VC_TYRE_LINEAR = 1 };
  * model's domain (Ux > 0 and s' = (Ux cos epsi - Uy sin epsi) / (1 - kappa ey) > 0 at every
  * stage, dynamic_car.py:169-191 divides by s') although every QP converged: the SQP started
  * from a warm start outside the domain and never got back in.  Not a solution of the NLP. */
-/* VC_INFEASIBLE (ABI 13, additive; kinematic stagewise kernel with vc_set_infeasibility on): the
+/* VC_INFEASIBLE (ABI 13, additive; kinematic stagewise kernel with vc_set_infeasibility on, or the
+ * condensed kernel on a vc_qp.solver = 2 context): the
  * QP's linearised rows C dz <= d have no feasible point, proved inside the interior point by a
  * Farkas vector (vc_get_farkas).  u* / x* / u0 are the warm start and its prediction (dz = 0).
  * Never reported unless the detection is on: such a QP then ends VC_MAX_ITER as before.
@@ -142,7 +143,11 @@ typedef struct vc_qp {
   int32_t solver;   /* solve-kernel choice (ABI 5).  Kinematic: 0 = condensed (kin_ltv.hip) where
                        built (N = 20) and kin_sqp == 0, else stagewise Riccati (kin_ric.hip);
                        1 = stagewise Riccati always; with vc_set_infeasibility on, 0 routes N = 20 to the
-                       stagewise kernel too (the detection lives there), as elastic > 0 does.
+                       stagewise kernel too, as elastic > 0 does; 2 = as 0, but vc_set_infeasibility
+                       does not reroute: where 0 would have chosen the condensed kernel, the detection
+                       runs inside it (kin_ltv_kernel<20, true>) at the condensed kernel's speed, and
+                       where 0 chooses the stagewise kernel anyway (N != 20, kin_sqp > 0, ms,
+                       elastic != 0), 2 does too.
                        Cascaded: 0 / 1 = stagewise Riccati (casc_ric.hip),
                        2 = condensed (casc_sqp.hip, M = 40 only).  Single-track: the dtype
                        picks the kernel (VC_F32: dyn_sqp.hip, VC_F64: st_sqp.hip). */
@@ -254,7 +259,12 @@ int vc_synchronize(vc_ctx* ctx);
  * always have a solution and are not tested.  On VC_INFEASIBLE iters is the count so far, the
  * outputs are the warm start and its prediction, and vc_solve_diag's diag[2] has bit 32 set.
  * Default off: the context then behaves exactly as before.  Turning it on routes an N = 20,
- * vc_qp.solver = 0 context to the stagewise kernel (see vc_qp.solver).  VC_E_UNSUPPORTED on
+ * vc_qp.solver = 0 context to the stagewise kernel (see vc_qp.solver); an N = 20, vc_qp.solver = 2
+ * context keeps the condensed kernel, which then runs the same test on the same rows (the problems
+ * it does not certify are solved bit for bit as with the detection off).  Where lam / |lam|_1 does
+ * not satisfy the inequality yet, the condensed kernel also tries the y made of the same state-row
+ * multipliers and the box-row weights that cancel C'y exactly (d'y < 0 alone is then the test); the
+ * y it returns satisfies the inequality above either way, and it certifies in fewer iterations.  VC_E_UNSUPPORTED on
  * dynamic / cascaded contexts and on kinematic horizons the stagewise kernel is not built for. */
 int vc_set_infeasibility(vc_ctx* ctx, int on, double eps);
 
@@ -383,6 +393,8 @@ int vc_solve_from(vc_ctx* ctx, int B, const void* x0, const void* kappa, const v
  *       converged, 4 = active-set polish certified, 8 = polish factorisation failed,
  *   [3] polish rounds used.  diag follows the pointer convention of `flags`.
  * Kinematic (kin_ltv) [0] is the true residual of the interior point's last iterate.
+ * Kinematic contexts with vc_set_infeasibility on (either kernel): [2] bit 32 = the QP was
+ * certified infeasible (status VC_INFEASIBLE; vc_get_farkas).
  * Single-track / cascaded SQP contexts: [2] = 1 any QP failed, 2 every QP converged,
  * 4 every converged QP's answer certified by the active-set polish, 16 the SQP stopped early (a QP after the first had no solution: its step was refused and
  * the earlier iterate returned, so `status` reflects the QPs before it only), 32 a QP was certified

@@ -10,8 +10,8 @@ make timing -j8 >/dev/null
 HIPCC=/opt/rocm/bin/hipcc
 FLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -I../../include -I. -Wall -Wno-unused-function"
 SRC=${SRC:-kin_ltv}
-ALL="vcmpc_abi kin_ltv kin_ric kin_merit dyn_sqp casc_sqp casc_ric st_sqp models track numerics"
-TIMED="vcmpc_abi kin_ltv kin_ric dyn_sqp casc_sqp casc_ric st_sqp"
+ALL="vcmpc_abi kin_ltv kin_ltv_det kin_ric kin_merit dyn_sqp casc_sqp casc_ric st_sqp models track numerics"
+TIMED="vcmpc_abi kin_ltv kin_ltv_det kin_ric dyn_sqp casc_sqp casc_ric st_sqp"
 case " $SRC " in " st_sqp "|" casc_ric "|" casc_sqp ") FLAGS="$FLAGS -mllvm -disable-machine-licm";; esac
 OTHER=""; OTHER_T=""
 for o in $ALL; do

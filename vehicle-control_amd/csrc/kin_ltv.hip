@@ -37,6 +37,11 @@
 #include "vc_models.hpp"
 #include "vcmpc.h"
 
+// 1 in kin_ltv_det.hip, which includes this file: kin_ltv_kernel<20, true> and launch_kin_ltv_det only
+#ifndef VC_KIN_LTV_DET
+#define VC_KIN_LTV_DET 0
+#endif
+
 #ifndef KIN_NU_TOL
 #define KIN_NU_TOL 1e-10  // CG also runs until the multiplier step R e is below this x scale (0: off)
 #endif
@@ -1130,7 +1135,19 @@ struct Side {
 
 }  // namespace
 
-template <int N>
+// DET (vc_set_infeasibility on a qp.solver = 2 context; launch_kin_ltv picks it from A.detect): the
+// interior point tests its multipliers for a Farkas certificate of infeasibility from the second
+// iteration on, as kin_ric_kernel<N, true> does (kin_ric.hip).  With C dz <= d the rows of
+// oracle/ltv_qp.py kin_qp, y = lam / |lam|_1 and R = sum over the inputs of max(d_up, d_dn) (a bound
+// on |dz|_1 inside the box), d'y + R |C'y|_inf < -detect_eps proves that no dz satisfies the rows:
+// the problem ends VC_INFEASIBLE with dz = 0 and y in A.farkas.  Where that y does not certify yet, the
+// same row multipliers are tried with the box multipliers that cancel C'y exactly (in the loop below);
+// the y returned satisfies the same inequality either way.  Everything the test adds is under
+// `if constexpr (DET)`: the DET = false kernel is the kernel without it.  The two instantiations are
+// compiled in translation units of their own (this file, and this file again through kin_ltv_det.hip):
+// side by side in one, the helpers above have two call sites each and the inliner hands the
+// DET = false kernel other code than it gets alone (the matrix-core sections are scheduled differently).
+template <int N, bool DET>
 __global__ __launch_bounds__(64) void kin_ltv_kernel(KinLtvArgs A) {
   using D = Dims<N>;
   constexpr int n = D::n, NC = D::NC;
@@ -1418,6 +1435,10 @@ __global__ __launch_bounds__(64) void kin_ltv_kernel(KinLtvArgs A) {
   cs.shi = cs.hasHi ? fmax(cs.hi, 1.0) : 1.0;
   cs.llo = cs.hasLo ? 1.0 : 0.0;
   cs.lhi = cs.hasHi ? 1.0 : 0.0;
+  // infeasibility test (DET): R bounds |dz|_1 of every dz inside the input box and trust region
+  [[maybe_unused]] double Rbox = 0.0, l1_inf = 1.0;
+  [[maybe_unused]] bool infeas = false;
+  if constexpr (DET) Rbox = wave_sum(lane < n ? fmax(bx.hi, -bx.lo) : 0.0);
 
   VC_TACC(T_SETUP, t_setup0)
   // ---- Phase 1: Mehrotra predictor-corrector interior point ------------------
@@ -1502,6 +1523,46 @@ __global__ __launch_bounds__(64) void kin_ltv_kernel(KinLtvArgs A) {
       last_res = res;
       last_mu = mu;
       if (converged || it >= max_iter || !isfinite(res) || !isfinite(mu)) break;
+      if constexpr (DET) {
+        if (it >= 1) {
+          // d'lam over all row sides (absent sides carry lam = 0), every rounding spelled out and no
+          // product the iteration forms named again (the note on mu above)
+          const double dcs = __builtin_fma(cs.hi, cs.lhi, -(cs.lo * cs.llo));  // the state rows' part
+          const double dl = wave_sum(__builtin_fma(bx.hi, bx.lhi, __builtin_fma(-bx.lo, bx.llo, dcs)));
+          if (dl < 0.0) {  // uniform; the G product only where the rows' bound can certify
+            const double l1 = wave_sum((bx.llo + bx.lhi) + (cs.llo + cs.lhi));
+            wave_sync();
+            s.vc[lane] = (lane < NC) ? (cs.lhi - cs.llo) : 0.0;
+            wave_sync();
+            const double gtl = gt_dot<N>(s, lane);  // s.vc is rewritten below before its next read
+            const double cmax = wave_max(lane < n ? fabs((bx.lhi - bx.llo) + gtl) : 0.0);
+            if (__builtin_fma(Rbox, cmax, dl) / l1 < -A.detect_eps) {
+              infeas = true;
+              l1_inf = l1;
+              break;
+            }
+            // Not yet: the same state-row multipliers with the box multipliers *completed* instead of the
+            // interior point's own.  q = G'(lhi - llo) is the state rows' part of C'lam; the box rows
+            // +e_j (weight max(-q_j, 0)) and -e_j (weight max(q_j, 0)) cancel it exactly, so C'y = 0 and
+            // the criterion is d'y < 0 alone, with d'y |y|_1 = sum dcs + sum_j (q_j > 0 ? d_dn : d_up)_j |q_j|
+            // -- the state rows' bound against the least q'dz over the box.  Sound for the same reason
+            // (y >= 0, |y|_1 = 1), and sharper while the interior point's box multipliers have not aligned
+            // with its row multipliers (R |C'y|_inf then dominates: DESIGN 14).  The problem is over once
+            // it holds, so the completed multipliers replace the box sides' for the certificate output.
+            const double q = lane < n ? gtl : 0.0;
+            const double aq = fabs(q);
+            const double l1s = wave_sum((cs.llo + cs.lhi) + aq);
+            const double dys = wave_sum(__builtin_fma(q > 0.0 ? -bx.lo : bx.hi, aq, dcs));
+            if (dys / l1s < -A.detect_eps) {
+              infeas = true;
+              l1_inf = l1s;
+              bx.lhi = fmax(-q, 0.0);
+              bx.llo = fmax(q, 0.0);
+              break;
+            }
+          }
+        }
+      }
       ++it;
       const double wlo_b = bx.hasLo ? bx.llo / bx.slo : 0.0;
       const double whi_b = bx.hasHi ? bx.lhi / bx.shi : 0.0;
@@ -1914,6 +1975,29 @@ __global__ __launch_bounds__(64) void kin_ltv_kernel(KinLtvArgs A) {
   else if (polished || converged) st = VC_SOLVED;
   else st = VC_MAX_ITER;
   if (!finite) z = 0.0;
+  if constexpr (DET) {
+    // VC_INFEASIBLE returns the warm start and its prediction (dz = 0); the certificate y = lam / |lam|_1
+    // goes out in the oracle's row order: the input rows of stage 0..N-1 (hi, lo of a, then of w),
+    // then per stage 1..N-1 the v row and the delta rows (hi, lo)
+    if (infeas) {
+      st = VC_INFEASIBLE;
+      z = 0.0;
+    }
+    if (A.farkas) {
+      double* fk = A.farkas + (size_t)b * (7 * N - 3);
+      if (lane < n) {
+        fk[2 * lane] = infeas ? bx.lhi / l1_inf : 0.0;
+        fk[2 * lane + 1] = infeas ? bx.llo / l1_inf : 0.0;
+      }
+      if (lane < N - 1) {
+        fk[4 * N + 3 * lane] = infeas ? cs.llo / l1_inf : 0.0;
+      } else if (lane < NC) {
+        const int r = lane - (N - 1);
+        fk[4 * N + 3 * r + 1] = infeas ? cs.lhi / l1_inf : 0.0;
+        fk[4 * N + 3 * r + 2] = infeas ? cs.llo / l1_inf : 0.0;
+      }
+    }
+  }
   wave_sync();
   if (lane < n) {
     s.vz[lane] = z;
@@ -1933,7 +2017,7 @@ __global__ __launch_bounds__(64) void kin_ltv_kernel(KinLtvArgs A) {
       A.diag[(size_t)b * DS + 0] = last_res / scale;
       A.diag[(size_t)b * DS + 1] = last_mu / scale;
       A.diag[(size_t)b * DS + 2] = double((chol_fail ? 1 : 0) | (converged ? 2 : 0) | (polished ? 4 : 0) |
-                                          (pchol_fail ? 8 : 0));
+                                          (pchol_fail ? 8 : 0) | (DET && infeas ? 32 : 0));
       A.diag[(size_t)b * DS + 3] = double(rounds);
     }
   }
@@ -2000,6 +2084,19 @@ __global__ __launch_bounds__(64) void kin_ltv_kernel(KinLtvArgs A) {
 #endif
 }
 
+#if VC_KIN_LTV_DET
+// this translation unit is kin_ltv_det.hip: the DET instantiation only (launch_kin_ltv hands over to it)
+hipError_t launch_kin_ltv_det(const KinLtvArgs& a, int N, hipStream_t stream) {
+  if (a.B <= 0) return hipSuccess;
+  switch (N) {
+    case 20:
+      hipLaunchKernelGGL((kin_ltv_kernel<20, true>), dim3(a.B), dim3(64), 0, stream, a);
+      return hipGetLastError();
+    default:
+      return hipErrorInvalidValue;
+  }
+}
+#else
 // Test hook (vc_debug_kin_gdots): grow_dot and gt_dot as the solver calls them, on operands the caller
 // gives -- G[B][NC][n], vz[B][n], vc[B][NC] -- all 64 lanes of each result to out_grow / out_gt[B][64]
 template <int N>
@@ -2038,13 +2135,16 @@ size_t kin_ltv_smem_bytes(int N) {
 
 hipError_t launch_kin_ltv(const KinLtvArgs& a, int N, hipStream_t stream) {
   if (a.B <= 0) return hipSuccess;
+  // vc_condense (mode 1) returns before the solve: the DET = false instantiation serves it
+  if (a.detect && a.mode == 0) return launch_kin_ltv_det(a, N, stream);
   switch (N) {
     case 20:
-      hipLaunchKernelGGL(kin_ltv_kernel<20>, dim3(a.B), dim3(64), 0, stream, a);
+      hipLaunchKernelGGL((kin_ltv_kernel<20, false>), dim3(a.B), dim3(64), 0, stream, a);
       return hipGetLastError();
     default:
       return hipErrorInvalidValue;
   }
 }
+#endif  // VC_KIN_LTV_DET
 
 }  // namespace vc

@@ -195,8 +195,9 @@ struct KinLtvArgs {
   vc_kin_mpc w;
   vc_qp qp;
   vc_obstacles obs;
-  // infeasibility detection (vc_set_infeasibility; kin_ric.hip only, appended so that the offsets
-  // kin_ltv.hip reads stay where they were)
+  // infeasibility detection (vc_set_infeasibility), appended so that the offsets kin_ltv.hip read
+  // before it stay where they were.  kin_ric.hip: every launch; kin_ltv.hip: mode 0 launches of a
+  // qp.solver = 2 context (the launchers pick the DET instantiation from `detect`)
   int detect;           // 1: the Farkas test runs inside the interior point (status VC_INFEASIBLE)
   double detect_eps;    // roundoff guard of the test
   double* farkas;       // [B][7N-3] certificate y in the row order of oracle/ltv_qp.py kin_qp, may be null
@@ -348,6 +349,8 @@ hipError_t launch_drive(const ModelArgs& m, int dtype, const TrackTable& tt, dou
                         void* x_ctx, const int32_t* status, void* xbar, void* ubar, int32_t* nfail, double* log_x,
                         void* log_u, const void* kappa, hipStream_t st);
 hipError_t launch_kin_ltv(const KinLtvArgs& a, int N, hipStream_t stream);
+// kin_ltv_det.hip: kin_ltv_kernel<N, true>; launch_kin_ltv hands a mode 0 launch with a.detect set over to it
+hipError_t launch_kin_ltv_det(const KinLtvArgs& a, int N, hipStream_t stream);
 // Stagewise-Riccati kinematic LTV-MPC step (kin_ric.hip): the same contract, any built N
 // (KinLtvArgs.mode / H_out / g_out are not read).
 hipError_t launch_kin_ric(const KinLtvArgs& a, int N, hipStream_t stream);

@@ -213,12 +213,15 @@ vc::TrackTable track_table(const vc_ctx* c) {
 // matches the oracle to 1e-8 there, the condensed normal equations to 8e-5; scripts/kin_sqp_debug.py)
 bool kin_condensed_cfg(const vc_ctx* c) {
   // elastic rows (qp.elastic) and multiple shooting are built in the stagewise kernel only
-  return vc::kin_ltv_smem_bytes(c->N) > 0 && c->p.qp.solver == 0 && c->p.qp.kin_sqp <= 0 && !c->p.qp.ms &&
-         c->p.qp.elastic == 0.0;
+  // (qp.solver = 2: as 0, with the infeasibility detection inside the condensed kernel -- below)
+  return vc::kin_ltv_smem_bytes(c->N) > 0 && (c->p.qp.solver == 0 || c->p.qp.solver == 2) && c->p.qp.kin_sqp <= 0 &&
+         !c->p.qp.ms && c->p.qp.elastic == 0.0;
 }
-// ... and so is the infeasibility detection (vc_set_infeasibility): the solve of a context that has it
-// on goes to the stagewise kernel; vc_condense keeps the condensed kernel's H, g either way
-bool kin_condensed(const vc_ctx* c) { return kin_condensed_cfg(c) && !c->det.on; }
+// The infeasibility detection (vc_set_infeasibility) is built in both kernels.  On a qp.solver = 0
+// context the solve of a context that has it on goes to the stagewise kernel (the routing since ABI 13);
+// qp.solver = 2 keeps the condensed kernel and its DET instantiation runs the test (kin_ltv.hip).
+// vc_condense keeps the condensed kernel's H, g either way.
+bool kin_condensed(const vc_ctx* c) { return kin_condensed_cfg(c) && (!c->det.on || c->p.qp.solver == 2); }
 bool kin_solve_built(const vc_ctx* c) {
   return c->model == VC_MODEL_KINEMATIC && c->dtype == VC_F64 && (kin_condensed(c) || vc::kin_ric_built(c->N));
 }
@@ -712,7 +715,9 @@ static int kin_solve(vc_ctx* c, int B, const void* x0, const void* kappa, const 
         a.diag = st.out(diag, (size_t)B * VC_DIAG_COLS * 8);
       }))
     return r;
-  arm_detection(c, a, B);  // kin_condensed(c) is false then: every launch below is the stagewise kernel's
+  // detection on: the launches below are the stagewise kernel's DET instantiation, or, where a
+  // qp.solver = 2 context keeps the condensed kernel (kin_condensed), kin_ltv_kernel<N, true>
+  arm_detection(c, a, B);
   const int S = c->p.qp.kin_sqp;
   if (S > 0 && (const void*)a.ubar != (const void*)a.u_out) {
     // the SQP iterates in place: start it on u_out (device pointers; staged, the two are one slice)

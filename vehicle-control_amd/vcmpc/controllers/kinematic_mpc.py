@@ -102,7 +102,12 @@ def horizon_params(s0, v_pred, mpc_dt, k_of_s):
 
 
 class BatchedKinematicMPC(Controller):
-    """B independent kinematic MPCs solved in one launch."""
+    """B independent kinematic MPCs solved in one launch.
+
+    ``qp: {detect_infeasible: true}`` in the config certifies first solves without a feasible point
+    (``infeasible_steps``); at horizon 20 that solve runs in the stagewise kernel unless the block
+    also says ``solver: 2``, which keeps the condensed kernel and runs the detection inside it:
+    ``qp: {solver: 2, detect_infeasible: true}``."""
 
     def __init__(self, car, config, batch: int, device: int = 0, seed: int | None = 31):
         super().__init__()

@@ -32,7 +32,11 @@ def _is_torch(a) -> bool:
 
 
 class Context:
-    """One solve context (one device, one model, one horizon, one stream)."""
+    """One solve context (one device, one model, one horizon, one stream).
+
+    ``detect_infeasible`` turns the model's in-kernel infeasibility detection on at creation.  On a
+    kinematic N = 20 context the params' ``qp.solver`` decides where it runs: 0 hands the solve to
+    the stagewise kernel while it is on, 2 keeps the condensed kernel and tests there."""
 
     def __init__(self, model: int = _abi.VC_MODEL_KINEMATIC, N: int = 20, max_batch: int = 1024,
                  dtype: int = _abi.VC_F64, device: int = 0, params: _abi.vc_params | None = None,
@@ -107,18 +111,23 @@ class Context:
                                               float(margin_min)))
 
     def set_infeasibility(self, on: bool, eps: float = 0.0):
-        """``vc_set_infeasibility``: in-kernel infeasibility detection of the stagewise kinematic
-        kernel.  On: a QP whose linearised rows have no feasible point ends with status
+        """``vc_set_infeasibility``: in-kernel infeasibility detection of the kinematic kernels.
+        On: a QP whose linearised rows have no feasible point ends with status
         ``VC_INFEASIBLE`` (4), proved by the Farkas vector ``farkas()`` returns; ``eps <= 0`` keeps
-        the default roundoff guard 1e-9.  Raises ``VcError`` (VC_E_UNSUPPORTED) on dynamic /
-        cascaded contexts."""
+        the default roundoff guard 1e-9.  An N = 20 ``qp.solver = 0`` context is solved by the
+        stagewise kernel while the detection is on; with ``qp.solver = 2`` it keeps the condensed
+        kernel, which runs the same test (the problems it does not certify come out bit for bit
+        as with the detection off).  Raises ``VcError`` (VC_E_UNSUPPORTED) on dynamic / cascaded
+        contexts."""
         self._set_detection(self.lib.vc_set_infeasibility, on, eps)
 
     def farkas(self, B: int | None = None):
         """``vc_get_farkas``: y[B, 7N - 3] of the last solve (rows in the order of
         oracle/ltv_qp.py ``kin_qp``; zero for problems that did not end ``VC_INFEASIBLE``), a
         numpy array after a host-array solve, a torch tensor on the context's device after a
-        device-tensor one.  Raises ``VcError`` when the detection is off."""
+        device-tensor one.  The stagewise kernel and the condensed one (``qp.solver = 2``) write the
+        same rows in the same order; the condensed one may return the row multipliers with the box
+        weights that cancel C'y instead of the interior point's own (the same inequality holds).  Raises ``VcError`` when the detection is off."""
         return self._certificates(self.lib.vc_get_farkas, B, 7 * self.N - 3, False)[0]
 
     def set_sqp_infeasibility(self, on: bool, eps: float = 0.0):
