@@ -471,6 +471,19 @@ int vc_debug_rcp(vc_ctx* ctx, int n, const void* x, void* out, int flags);
 int vc_debug_kin_gdots(vc_ctx* ctx, int B, const void* G, const void* vz, const void* vc, void* out_grow,
                        void* out_gt, int flags);
 
+/* Test diagnostics (kinematic fp64 contexts, N = 20): the fused kernel's triangular solves, evaluated
+ * by the device function the solver calls (csrc/kin_ltv.hip chol_solve) on a factor given here, B
+ * (<= max_batch) independent sets: L[B][2N][2N] row-major, dinv[B][2N] (the inverse pivots the sweeps
+ * multiply by; the diagonal of L is not read), b[B][64] (lane j's right-hand side), fp64.  Lane j's
+ * row registers take row j of L whole and the LDS columns take the entries on and below the diagonal,
+ * so the caller decides what the sweeps find on and above it: they must not let it act.
+ * out[B][64] = all 64 lanes of the result, x_j in lane j < 2N and +0 in the lanes beyond.
+ * Operation sequence: forward, k = 0..2N-1: p = RN(acc_k dinv_k), acc_i = fma(-L[i][k], p, acc_i) for
+ * i > k; y = RN(acc dinv); backward, k = 2N-1..0: x_k = RN(acc_k dinv_k), acc_i = fma(-L[k][i], x_k,
+ * acc_i) for i < k.  No reference counterpart. */
+int vc_debug_kin_trisolve(vc_ctx* ctx, int B, const void* L, const void* dinv, const void* b, void* out,
+                          int flags);
+
 /* Predict: xbar[B][N+1][nx] from x0[B][nx] and ubar[B][N][nu] (spatial step). */
 int vc_rollout(vc_ctx* ctx, int B, const void* x0, const void* ubar, const void* kappa,
                const void* ds, void* xbar, int flags);

@@ -86,10 +86,6 @@
 // direction) that the oracle certificate catches (scripts/kin_hole_diag.py, profiles/r06/kin_ab/*_r06z[ijk].*)
 #define KIN_STEP_F 0.99
 #endif
-#ifndef KIN_SOLVE_CH
-#define KIN_SOLVE_CH 8  // backward-sweep steps per prefetched chunk of the triangular solves (divides 2N;
-                        // 4 / 10 within noise of 8, as KIN_DOT_CH 4 / 12: profiles/r06/kin_ab/kin_polish_ab_c2_r06zg.log)
-#endif
 #ifndef KIN_PANEL_CH
 #define KIN_PANEL_CH 6  // columns per in-panel update chunk of factor_blocked, loaded one chunk ahead (2 / 4 / 8:
                         // C2 +1.2 / +1.0 / +0.8 %, bit-identical; profiles/r06/kin_ab/kin_polish_ab_c2_r06ze.log)
@@ -352,7 +348,7 @@ struct GSplit {
   // gt_dot.  Column j is nonzero at rows r >= j/2 (v rows) and r >= j/2 + N (delta rows): long
   // columns j < 20, partner lanes n..n+19; short columns j >= 20 read the rows 10..18 | 28..36 |
   // 11..17 | 29..37, shifts +10, +18, -9, +1 against the long lanes' row 2t in the four segments
-  static constexpr int COL_LONG = n / 2;
+  static constexpr int COL_LONG = n / 2, COL_D2 = 9;  // segment 2 reads row 2t - 9 + its base's shift
   static_assert(n + COL_LONG <= 64, "partner lanes of the long columns");
 };
 
@@ -408,55 +404,104 @@ __device__ __forceinline__ double gsplit_chain(const uint32_t (&g)[4], const uin
   return acc;
 }
 
+// The lane plan of the two products: every lane's segment base addresses and its partner's byte lane.
+// They depend on the lane alone, so the kernel works them out once (gplan_make, after the input load) and
+// parks them in accumulator registers, as RowRegs does with the factor's row: 14 registers that no VALU
+// instruction can address, out of the vector file for the whole solve.  A product brings its five or
+// nine values back with one v_accvgpr_read_b32 each, in one volatile asm statement: not hoisted out of
+// the solver loops (hoisted copies in VGPRs spilled), not recomputed either (the
+// address arithmetic and lane-class selects were 39 of gt_dot's 110 instructions and 18 of grow_dot's).
+template <int N>
+struct GPlan {
+  int rg0, rg2, rv0, rv2, rf;  // grow_dot: G and vz bases of steps 0..9 and 10..18, the partner's byte lane
+  int cg[4], cv[4], cf;        // gt_dot: G and vc bases of the four segments, the partner's byte lane
+};
+__device__ __forceinline__ int agpr_put(uint32_t v) {
+  int a;
+  asm("v_accvgpr_write_b32 %0, %1" : "=a"(a) : "v"(v));
+  return a;
+}
+template <int N>
+__device__ __forceinline__ GPlan<N> gplan_make(const Smem<N>& s, int lane) {
+  using P = GSplit<N>;
+  constexpr int n = P::n, NC = P::NC, LD = P::LD;
+  const int l = lane_opaque(lane);
+  GPlan<N> pl;
+  {  // grow_dot
+    const bool part = l >= NC;
+    const bool shrt = uint32_t(l) < uint32_t(P::ROW_SHORT) || uint32_t(l - (N - 1)) < uint32_t(P::ROW_SHORT);
+    // partner lane NC + q: row q + 9 (q < 10), q + 18 (q < 20), the zero row NC beyond
+    const int r = min(part ? l - (l < NC + (N - 1 - P::ROW_SHORT) ? NC - P::ROW_SHORT : N) : l, NC);
+    const uint32_t odd = part ? 8u : 0u;                   // partners start at index 1
+    const uint32_t fwd = shrt ? 0u : 8u * uint32_t(P::T);  // steps >= 10 read index 2t - 19 + this: short rows 1, 3, ..
+    const uint32_t g0 = (uint32_t)(uintptr_t)(lds_cdouble*)&s.G[0][0] + uint32_t(r) * (8u * LD) + odd;
+    const uint32_t v0 = (uint32_t)(uintptr_t)(lds_cdouble*)&s.vz[0] + odd;
+    pl.rg0 = agpr_put(g0);
+    pl.rg2 = agpr_put(g0 + fwd);
+    pl.rv0 = agpr_put(v0);
+    pl.rv2 = agpr_put(v0 + fwd);
+    pl.rf = agpr_put(uint32_t(4 * (l + (l < N - 1 ? NC - P::ROW_SHORT : N))));  // long row: its partner
+  }
+  {  // gt_dot
+    const bool part = l >= n;
+    const bool shrt = uint32_t(l - P::COL_LONG) < uint32_t(n - P::COL_LONG);
+    const int j = part ? l - n : l;  // lanes n+20.. repeat columns 20..23 (discarded)
+    const uint32_t ms = shrt ? 1u : 0u, mp = part ? 1u : 0u;
+    const uint32_t gp = (uint32_t)(uintptr_t)(lds_cdouble*)&s.G[0][0] + uint32_t(j) * 8u + mp * (8u * LD);
+    const uint32_t vp = (uint32_t)(uintptr_t)(lds_cdouble*)&s.vc[0] + mp * 8u;
+    // rows read in segment k: 2t - D[k] + (short columns SH[k], long ones D[k], partners D[k] + 1)
+    constexpr int SH[4] = {10, 18, 0, 1};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int D = k == 2 ? P::COL_D2 : 0;
+      pl.cg[k] = agpr_put(gp + uint32_t(D * 8 * LD) + ms * uint32_t((SH[k] - D) * 8 * LD));
+      pl.cv[k] = agpr_put(vp + uint32_t(D * 8) + ms * uint32_t((SH[k] - D) * 8));
+    }
+    pl.cf = agpr_put(uint32_t(4 * (l + n)));  // long column j: lane n + j
+  }
+  return pl;
+}
+
 // y_r = G_r . v for lane r (v broadcast in s.vz), 0 in lanes >= NC.  Every lane of the wave must call it
 // (the long rows' odd chains run in lanes NC..NC+19).  Reads G[r][0..37], vz[0..37] as the 38-term form.
+// A short row's two base pairs are equal (its steps >= 10 read 2t - 19 from the same base): that is its flag.
 template <int N>
-__device__ double grow_dot(const Smem<N>& s, int lane) {
+__device__ double grow_dot(const GPlan<N>& pl, int lane) {
   using P = GSplit<N>;
-  constexpr int NC = P::NC, LD = P::LD;
-  const int l = lane_opaque(lane);  // the bases are recomputed here, not hoisted out of the loops
-  const bool part = l >= NC;
-  const bool shrt = uint32_t(l) < uint32_t(P::ROW_SHORT) || uint32_t(l - (N - 1)) < uint32_t(P::ROW_SHORT);
-  // partner lane NC + q: row q + 9 (q < 10), q + 18 (q < 20), the zero row NC beyond
-  const int r = min(part ? l - (l < NC + (N - 1 - P::ROW_SHORT) ? NC - P::ROW_SHORT : N) : l, NC);
-  const uint32_t odd = part ? 8u : 0u;                      // partners start at index 1
-  const uint32_t fwd = shrt ? 0u : 8u * uint32_t(P::T);     // steps >= 10 read index 2t - 19 + this: short rows 1, 3, ..
-  const uint32_t g0 = (uint32_t)(uintptr_t)(lds_cdouble*)&s.G[0][0] + uint32_t(r) * (8u * LD) + odd;
-  const uint32_t v0 = (uint32_t)(uintptr_t)(lds_cdouble*)&s.vz[0] + odd;
-  const uint32_t g[4] = {g0, g0, g0 + fwd, g0 + fwd}, v[4] = {v0, v0, v0 + fwd, v0 + fwd};
+  uint32_t g0, g2, v0, v2, f;
+  asm volatile("v_accvgpr_read_b32 %0, %5\n\tv_accvgpr_read_b32 %1, %6\n\tv_accvgpr_read_b32 %2, %7\n\t"
+               "v_accvgpr_read_b32 %3, %8\n\tv_accvgpr_read_b32 %4, %9"
+               : "=v"(g0), "=v"(g2), "=v"(v0), "=v"(v2), "=v"(f)
+               : "a"(pl.rg0), "a"(pl.rg2), "a"(pl.rv0), "a"(pl.rv2), "a"(pl.rf));
+  const bool shrt = g2 == g0;
+  const uint32_t g[4] = {g0, g0, g2, g2}, v[4] = {v0, v0, v2, v2};
   double stash;
   const double acc = gsplit_chain<N, 1, P::T, P::T>(g, v, shrt, stash);
-  const double other = lane_fetch(acc, 4 * (l + (l < N - 1 ? NC - P::ROW_SHORT : N)));  // long row: its partner
+  const double other = lane_fetch(acc, int(f));
   const double y = acc + (shrt ? stash : other);
-  return l < NC ? y : 0.0;
+  return lane_opaque(lane) < P::NC ? y : 0.0;
 }
 
 // (G' v)_j for lane j (v broadcast in s.vc), 0 in lanes >= n.  Every lane of the wave must call it (the
 // long columns' odd chains run in lanes n..n+19).  Reads rows 0..37 of G and vc[0..37] as the 38-term form.
+// A long column's (and a partner's) first two segments share a base, a short column's lie 8 rows apart:
+// that is its flag.
 template <int N>
-__device__ double gt_dot(const Smem<N>& s, int lane) {
+__device__ double gt_dot(const GPlan<N>& pl, int lane) {
   using P = GSplit<N>;
-  constexpr int n = P::n, LD = P::LD;
-  const int l = lane_opaque(lane);
-  const bool part = l >= n;
-  const bool shrt = uint32_t(l - P::COL_LONG) < uint32_t(n - P::COL_LONG);
-  const int j = part ? l - n : l;  // lanes n+20.. repeat columns 20..23 (discarded)
-  const uint32_t ms = shrt ? 1u : 0u, mp = part ? 1u : 0u;
-  const uint32_t gp = (uint32_t)(uintptr_t)(lds_cdouble*)&s.G[0][0] + uint32_t(j) * 8u + mp * (8u * LD);
-  const uint32_t vp = (uint32_t)(uintptr_t)(lds_cdouble*)&s.vc[0] + mp * 8u;
-  // rows read in segment k: 2t - D[k] + (short columns SH[k], long ones D[k], partners D[k] + 1)
-  constexpr int SH[4] = {10, 18, 0, 1}, D[4] = {0, 0, 9, 0};
-  uint32_t g[4], v[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    g[k] = gp + uint32_t(D[k] * 8 * LD) + ms * uint32_t((SH[k] - D[k]) * 8 * LD);
-    v[k] = vp + uint32_t(D[k] * 8) + ms * uint32_t((SH[k] - D[k]) * 8);
-  }
+  uint32_t g[4], v[4], f;
+  asm volatile("v_accvgpr_read_b32 %0, %9\n\tv_accvgpr_read_b32 %1, %10\n\tv_accvgpr_read_b32 %2, %11\n\t"
+               "v_accvgpr_read_b32 %3, %12\n\tv_accvgpr_read_b32 %4, %13\n\tv_accvgpr_read_b32 %5, %14\n\t"
+               "v_accvgpr_read_b32 %6, %15\n\tv_accvgpr_read_b32 %7, %16\n\tv_accvgpr_read_b32 %8, %17"
+               : "=v"(g[0]), "=v"(g[1]), "=v"(g[2]), "=v"(g[3]), "=v"(v[0]), "=v"(v[1]), "=v"(v[2]), "=v"(v[3]), "=v"(f)
+               : "a"(pl.cg[0]), "a"(pl.cg[1]), "a"(pl.cg[2]), "a"(pl.cg[3]), "a"(pl.cv[0]), "a"(pl.cv[1]),
+                 "a"(pl.cv[2]), "a"(pl.cv[3]), "a"(pl.cf));
+  const bool shrt = g[1] != g[0];
   double stash;
-  const double acc = gsplit_chain<N, LD, D[2], D[3]>(g, v, shrt, stash);
-  const double other = lane_fetch(acc, 4 * (l + n));  // long column j: lane n + j
+  const double acc = gsplit_chain<N, P::LD, P::COL_D2, 0>(g, v, shrt, stash);
+  const double other = lane_fetch(acc, int(f));
   const double y = acc + (shrt ? stash : other);
-  return l < n ? y : 0.0;
+  return lane_opaque(lane) < P::n ? y : 0.0;
 }
 
 
@@ -564,86 +609,139 @@ __device__ __forceinline__ void row_put(RowRegs<N>& R, int k, double v) {
   "v_accvgpr_read_b32 v255, %[h" #k "]\n\t"      \
   "v_fma_f64 %[acc], -v[254:255], vcc, %[acc]\n\t"
 #define KIN_FS_ROW(k) [l##k] "a"(Lr.lo[k]), [h##k] "a"(Lr.hi[k])
+#define KIN_FS_STEPS                                                 \
+  KIN_FS_STEP(0,63,1) KIN_FS_STEP(1,62,2) KIN_FS_STEP(2,61,3)        \
+  KIN_FS_STEP(3,60,4) KIN_FS_STEP(4,59,5) KIN_FS_STEP(5,58,6)        \
+  KIN_FS_STEP(6,57,7) KIN_FS_STEP(7,56,8) KIN_FS_STEP(8,55,9)        \
+  KIN_FS_STEP(9,54,10) KIN_FS_STEP(10,53,11) KIN_FS_STEP(11,52,12)   \
+  KIN_FS_STEP(12,51,13) KIN_FS_STEP(13,50,14) KIN_FS_STEP(14,49,15)  \
+  KIN_FS_STEP(15,48,16) KIN_FS_STEP(16,47,17) KIN_FS_STEP(17,46,18)  \
+  KIN_FS_STEP(18,45,19) KIN_FS_STEP(19,44,20) KIN_FS_STEP(20,43,21)  \
+  KIN_FS_STEP(21,42,22) KIN_FS_STEP(22,41,23) KIN_FS_STEP(23,40,24)  \
+  KIN_FS_STEP(24,39,25) KIN_FS_STEP(25,38,26) KIN_FS_STEP(26,37,27)  \
+  KIN_FS_STEP(27,36,28) KIN_FS_STEP(28,35,29) KIN_FS_STEP(29,34,30)  \
+  KIN_FS_STEP(30,33,31) KIN_FS_STEP(31,32,32) KIN_FS_STEP(32,31,33)  \
+  KIN_FS_STEP(33,30,34) KIN_FS_STEP(34,29,35) KIN_FS_STEP(35,28,36)  \
+  KIN_FS_STEP(36,27,37) KIN_FS_STEP(37,26,38) KIN_FS_STEP(38,25,39)  \
+  KIN_FS_STEP(39,24,40)
+#define KIN_FS_ROWS                                                                                       \
+  KIN_FS_ROW(0), KIN_FS_ROW(1), KIN_FS_ROW(2), KIN_FS_ROW(3), KIN_FS_ROW(4), KIN_FS_ROW(5),               \
+  KIN_FS_ROW(6), KIN_FS_ROW(7), KIN_FS_ROW(8), KIN_FS_ROW(9), KIN_FS_ROW(10), KIN_FS_ROW(11),             \
+  KIN_FS_ROW(12), KIN_FS_ROW(13), KIN_FS_ROW(14), KIN_FS_ROW(15), KIN_FS_ROW(16), KIN_FS_ROW(17),         \
+  KIN_FS_ROW(18), KIN_FS_ROW(19), KIN_FS_ROW(20), KIN_FS_ROW(21), KIN_FS_ROW(22), KIN_FS_ROW(23),         \
+  KIN_FS_ROW(24), KIN_FS_ROW(25), KIN_FS_ROW(26), KIN_FS_ROW(27), KIN_FS_ROW(28), KIN_FS_ROW(29),         \
+  KIN_FS_ROW(30), KIN_FS_ROW(31), KIN_FS_ROW(32), KIN_FS_ROW(33), KIN_FS_ROW(34), KIN_FS_ROW(35),         \
+  KIN_FS_ROW(36), KIN_FS_ROW(37), KIN_FS_ROW(38), KIN_FS_ROW(39)
 template <int N>
 __device__ __forceinline__ void forward_sweep(const RowRegs<N>& Lr, double& acc, double dj) {
   static_assert(Dims<N>::n == 40, "the sweep's 40 steps are written out");
   asm("s_mov_b64 s[98:99], exec\n\t"
-      KIN_FS_STEP(0,63,1) KIN_FS_STEP(1,62,2) KIN_FS_STEP(2,61,3)
-      KIN_FS_STEP(3,60,4) KIN_FS_STEP(4,59,5) KIN_FS_STEP(5,58,6)
-      KIN_FS_STEP(6,57,7) KIN_FS_STEP(7,56,8) KIN_FS_STEP(8,55,9)
-      KIN_FS_STEP(9,54,10) KIN_FS_STEP(10,53,11) KIN_FS_STEP(11,52,12)
-      KIN_FS_STEP(12,51,13) KIN_FS_STEP(13,50,14) KIN_FS_STEP(14,49,15)
-      KIN_FS_STEP(15,48,16) KIN_FS_STEP(16,47,17) KIN_FS_STEP(17,46,18)
-      KIN_FS_STEP(18,45,19) KIN_FS_STEP(19,44,20) KIN_FS_STEP(20,43,21)
-      KIN_FS_STEP(21,42,22) KIN_FS_STEP(22,41,23) KIN_FS_STEP(23,40,24)
-      KIN_FS_STEP(24,39,25) KIN_FS_STEP(25,38,26) KIN_FS_STEP(26,37,27)
-      KIN_FS_STEP(27,36,28) KIN_FS_STEP(28,35,29) KIN_FS_STEP(29,34,30)
-      KIN_FS_STEP(30,33,31) KIN_FS_STEP(31,32,32) KIN_FS_STEP(32,31,33)
-      KIN_FS_STEP(33,30,34) KIN_FS_STEP(34,29,35) KIN_FS_STEP(35,28,36)
-      KIN_FS_STEP(36,27,37) KIN_FS_STEP(37,26,38) KIN_FS_STEP(38,25,39)
-      KIN_FS_STEP(39,24,40)
+      KIN_FS_STEPS
       "s_mov_b64 exec, s[98:99]"
       : [acc] "+v"(acc)
-      : [dj] "v"(dj),
-        KIN_FS_ROW(0), KIN_FS_ROW(1), KIN_FS_ROW(2), KIN_FS_ROW(3), KIN_FS_ROW(4), KIN_FS_ROW(5),
-        KIN_FS_ROW(6), KIN_FS_ROW(7), KIN_FS_ROW(8), KIN_FS_ROW(9), KIN_FS_ROW(10), KIN_FS_ROW(11),
-        KIN_FS_ROW(12), KIN_FS_ROW(13), KIN_FS_ROW(14), KIN_FS_ROW(15), KIN_FS_ROW(16), KIN_FS_ROW(17),
-        KIN_FS_ROW(18), KIN_FS_ROW(19), KIN_FS_ROW(20), KIN_FS_ROW(21), KIN_FS_ROW(22), KIN_FS_ROW(23),
-        KIN_FS_ROW(24), KIN_FS_ROW(25), KIN_FS_ROW(26), KIN_FS_ROW(27), KIN_FS_ROW(28), KIN_FS_ROW(29),
-        KIN_FS_ROW(30), KIN_FS_ROW(31), KIN_FS_ROW(32), KIN_FS_ROW(33), KIN_FS_ROW(34), KIN_FS_ROW(35),
-        KIN_FS_ROW(36), KIN_FS_ROW(37), KIN_FS_ROW(38), KIN_FS_ROW(39)
+      : [dj] "v"(dj), KIN_FS_ROWS
       : "vcc", "s98", "s99", "v252", "v253", "v254", "v255");
 }
-#undef KIN_FS_STEP
-#undef KIN_FS_ROW
 
-// Solve (L L') x = b, lane j holding b_j; returns x_j.  Forward sweep (forward_sweep): y_k =
-// acc_k / L_kk is broadcast from lane k, and the lanes below subtract L[lane][k] y_k from their
-// accumulators, so lane k's accumulator stops changing once y_k is taken and y = acc / L_kk at
-// the end -- no per-step select.  Backward
-// sweep: lane i reads L[k][i] (row k of the packed rows, store_rows; or column i of the factor)
-// from LDS at immediate offsets of one per-lane base, prefetched one 8-step chunk ahead, and x_i
-// is written into lane i at step i by v_writelane (entries k <= i of the read are other rows'
-// storage: after step i they no longer matter) -- cheaper than a zero-or-entry address select
-// per element.  (A four-unknown blocked variant
-// was 13 % slower: the sweeps are bound by instruction issue, profiles/r03/section_cycles_r03g.txt.)
+// acc -= L[k][lane] * (acc * dj of lane k) on lanes < k, for k = n-1..1: the backward sweep, the same
+// way.  Lane i reads L[k][i], k > i, from column i of the factor in LDS (Lc, lc_base) at immediate
+// offsets of its column's byte address %[col].
+//   - Lane i's accumulator stops changing once x_i is taken (step i): step k's fma runs under EXEC =
+//     lanes 0..k-1, so what lane i would read at k <= i -- other columns' storage -- is never
+//     multiplied, x_i is not captured by v_writelane at step i but formed for every lane at once by one
+//     product after the sweep (the operands are the ones step i broadcast: same bits), and no lane
+//     needs a zero row to read from.  Step 0 has no fma.  The product of step k is needed from lane k,
+//     which the previous step's mask (lanes 0..k) still covers.
+//   - The operands come in pairs, ds_read_b128 of L[2p][i], L[2p+1][i] (lc_base is even: 16-byte
+//     aligned), into a ring of four fixed register quadruples v[236:251], pair p in quadruple p % 4,
+//     three pairs (six steps) ahead of their first use.  The reads run under the step's EXEC, so
+//     the finished lanes issue none (their addresses are the ones that conflicted).  LDS returns a
+//     wave's reads in order: s_waitcnt lgkmcnt(W) with W the number of pairs issued behind the one
+//     needed; the last one, lgkmcnt(0), leaves nothing outstanding behind the statement.
+//   - The two wait states between the second v_readlane and the fma are the s_waitcnt and the next
+//     read (odd k, a pair's first use: seven issue turns) or one s_nop 1 (even k: six).
+#define KIN_BS_Q0 "v[236:239]"
+#define KIN_BS_Q1 "v[240:243]"
+#define KIN_BS_Q2 "v[244:247]"
+#define KIN_BS_Q3 "v[248:251]"
+#define KIN_BS_L0 "v[236:237]"
+#define KIN_BS_H0 "v[238:239]"
+#define KIN_BS_L1 "v[240:241]"
+#define KIN_BS_H1 "v[242:243]"
+#define KIN_BS_L2 "v[244:245]"
+#define KIN_BS_H2 "v[246:247]"
+#define KIN_BS_L3 "v[248:249]"
+#define KIN_BS_H3 "v[250:251]"
+#define KIN_BS_HEAD(k)                       \
+  "v_mul_f64 v[252:253], %[acc], %[dj]\n\t"  \
+  "s_bfm_b64 exec, " #k ", 0\n\t"            \
+  "v_readlane_b32 vcc_lo, v252, " #k "\n\t"  \
+  "v_readlane_b32 vcc_hi, v253, " #k "\n\t"
+#define KIN_BS_FMA(reg) "v_fma_f64 %[acc], -" reg ", vcc, %[acc]\n\t"
+#define KIN_BS_READ(q, off) "ds_read_b128 " KIN_BS_Q##q ", %[col] offset:" #off "\n\t"
+// steps 2p+1 and 2p on pair p (quadruple q = p % 4); the odd step waits for its pair, then reads pair
+// p - 3 into quadruple rq (pair p + 1's, whose last use was the step before)
+#define KIN_BS_EVEN(k, q) KIN_BS_HEAD(k) "s_nop 1\n\t" KIN_BS_FMA(KIN_BS_L##q)
+#define KIN_BS_ODD(k, q, w) KIN_BS_HEAD(k) "s_waitcnt lgkmcnt(" #w ")\n\ts_nop 0\n\t" KIN_BS_FMA(KIN_BS_H##q)
+#define KIN_BS_PAIR(ko, ke, q, rq, off)                                                          \
+  KIN_BS_HEAD(ko) "s_waitcnt lgkmcnt(2)\n\t" KIN_BS_READ(rq, off) KIN_BS_FMA(KIN_BS_H##q) KIN_BS_EVEN(ke, q)
+#define KIN_BS_PAIR_NR(ko, ke, q, w) KIN_BS_ODD(ko, q, w) KIN_BS_EVEN(ke, q)
+#define KIN_BS_STEPS                                                                                  \
+  KIN_BS_PAIR(39,38,3,0,256) KIN_BS_PAIR(37,36,2,3,240) KIN_BS_PAIR(35,34,1,2,224)                    \
+  KIN_BS_PAIR(33,32,0,1,208) KIN_BS_PAIR(31,30,3,0,192) KIN_BS_PAIR(29,28,2,3,176)                    \
+  KIN_BS_PAIR(27,26,1,2,160) KIN_BS_PAIR(25,24,0,1,144) KIN_BS_PAIR(23,22,3,0,128)                    \
+  KIN_BS_PAIR(21,20,2,3,112) KIN_BS_PAIR(19,18,1,2,96) KIN_BS_PAIR(17,16,0,1,80)                      \
+  KIN_BS_PAIR(15,14,3,0,64) KIN_BS_PAIR(13,12,2,3,48) KIN_BS_PAIR(11,10,1,2,32)                       \
+  KIN_BS_PAIR(9,8,0,1,16) KIN_BS_PAIR(7,6,3,0,0) KIN_BS_PAIR_NR(5,4,2,2) KIN_BS_PAIR_NR(3,2,1,1)     \
+  KIN_BS_ODD(1,0,0)
+
+// Solve (L L') x = b, lane j holding b_j; returns x_j, +0 in lanes >= n.  ONE asm statement: the first
+// three operand pairs of the backward sweep are requested, then the forward sweep (forward_sweep's steps:
+// y_k = acc_k / L_kk is broadcast from lane k, and the lanes below subtract L[lane][k] y_k from their
+// accumulators), y = acc / L_kk, the backward sweep (above) and x = acc / L_kk.  Lanes >= n run the
+// forward sweep on meaningless row registers and no backward step: the select at the end gives them +0.
+// The statement reads LDS (the factor's columns), hence volatile and the memory clobber.  (A
+// four-unknown blocked variant was 13 % slower: the sweeps are bound by instruction issue,
+// profiles/r03/section_cycles_r03g.txt.)
+// dj: this lane's inverse pivot s.dinv[row], which a caller with several solves on one factor reads once.
+template <int N>
+__device__ double chol_solve(const RowRegs<N>& Lr, const Smem<N>& s, double b, int lane, double dj) {
+  constexpr int n = Dims<N>::n;
+  static_assert(n == 40, "the sweeps' 40 steps are written out");
+  const int row = lane < n ? lane : 0;
+  // col + 8 k = &L[k][row] for k > row
+  const uint32_t col = (uint32_t)(uintptr_t)lds_opaque(&s.Lc[lc_base<n>(row)]);
+  double acc = b;
+  asm volatile("s_mov_b64 s[98:99], exec\n\t"
+               KIN_BS_READ(3, 304) KIN_BS_READ(2, 288) KIN_BS_READ(1, 272)
+               KIN_FS_STEPS  // L y = b
+               "s_mov_b64 exec, s[98:99]\n\t"
+               "v_mul_f64 %[acc], %[acc], %[dj]\n\t"  // y
+               KIN_BS_STEPS  // L' x = y
+               "s_mov_b64 exec, s[98:99]\n\t"
+               "v_mul_f64 %[acc], %[acc], %[dj]"  // x
+               : [acc] "+v"(acc)
+               : [dj] "v"(dj), [col] "v"(col), KIN_FS_ROWS
+               : "vcc", "s98", "s99", "v236", "v237", "v238", "v239", "v240", "v241", "v242", "v243", "v244", "v245",
+                 "v246", "v247", "v248", "v249", "v250", "v251", "v252", "v253", "v254", "v255", "memory");
+  return lane < n ? acc : 0.0;
+}
 template <int N>
 __device__ double chol_solve(const RowRegs<N>& Lr, const Smem<N>& s, double b, int lane) {
-  constexpr int n = Dims<N>::n;
-  constexpr int CH = KIN_SOLVE_CH;
-  static_assert(n % CH == 0, "backward prefetch chunks");
-  const int row = lane < n ? lane : 0;
-  lds_cdouble* col = lds_opaque(&s.Lc[lc_base<n>(row)]);  // col[k] = L[k][row] for k > row
-  const double dj = s.dinv[row];
-  double acc = b;
-  forward_sweep<N>(Lr, acc, dj);  // L y = b
-  acc *= dj;                      // y
-  double x = 0.0;
-  double lk[2][CH];
-  lds_cdouble* zero = lds_opaque(&s.zrow[0]);
-  auto fetch = [&](int c, int buf) {  // L[k][row] for k = n-1-c*CH ... n-CH-c*CH
-    // a lane whose row is at or below every k of the chunk reads zeros at one shared address
-    // (broadcast) instead of the previous columns' storage (distinct addresses: bank conflicts)
-    lds_cdouble* src = row < n - 1 - c * CH ? col : zero;
-#pragma unroll
-    for (int q = 0; q < CH; ++q) lk[buf][q] = src[n - 1 - c * CH - q];
-  };
-  fetch(0, 0);
-#pragma unroll
-  for (int c = 0; c < n / CH; ++c) {  // L' x = y: lane i < k needs L[k][i]
-    if (c + 1 < n / CH) fetch(c + 1, (c + 1) & 1);
-    fence();
-#pragma unroll
-    for (int q = 0; q < CH; ++q) {
-      const int k = n - 1 - c * CH - q;
-      const double xk = lane_bcast(acc * dj, k);
-      x = lane_put(x, xk, k);
-      acc -= lk[c & 1][q] * xk;
-    }
-    fence();
-  }
-  return x;
+  return chol_solve<N>(Lr, s, b, lane, s.dinv[lane < Dims<N>::n ? lane : 0]);
 }
+#undef KIN_BS_STEPS
+#undef KIN_BS_PAIR_NR
+#undef KIN_BS_PAIR
+#undef KIN_BS_ODD
+#undef KIN_BS_EVEN
+#undef KIN_BS_READ
+#undef KIN_BS_FMA
+#undef KIN_BS_HEAD
+#undef KIN_FS_STEPS
+#undef KIN_FS_ROWS
+#undef KIN_FS_STEP
+#undef KIN_FS_ROW
 
 // Nonzero extent of row r of the two LDS row sets the matrix cores take Gram matrices of:
 // ROWS_G, the constraint rows of G (row r is zero beyond column 2 crow_stage(r): stage k's
@@ -1174,6 +1272,7 @@ __global__ __launch_bounds__(64) void kin_ltv_kernel(KinLtvArgs A) {
   for (int i = lane; i < 2 * D::LD; i += 64) (&s.G[NC][0])[i] = 0.0;  // zero rows NC, NC+1
   if (lane < 48) s.zrow[lane] = 0.0;
   if (lane == 0) s.Lc[Smem<N>::LC_ZERO] = 0.0;
+  const GPlan<N> gpl = gplan_make<N>(s, lane);  // the G products' lane plan, in accumulator registers from here on
   wave_sync();
 
   VC_TSTAMP(t_sweep0)
@@ -1468,13 +1567,13 @@ __global__ __launch_bounds__(64) void kin_ltv_kernel(KinLtvArgs A) {
     s.vz[lane] = (lane < n) ? z : 0.0;
     s.vc[lane] = (lane < NC) ? (cs.lhi - cs.llo) : 0.0;
     wave_sync();
-    const double yc = grow_dot<N>(s, lane);
+    const double yc = grow_dot<N>(gpl, lane);
     // H z and G' lambda outside the select, every lane taking part (lanes >= n repeat row 0 of H
     // and run the long columns' odd chains of G')
     fence();
     const double hz = h_dot<N>(s, lane);
     fence();
-    const double gtl = gt_dot<N>(s, lane);
+    const double gtl = gt_dot<N>(gpl, lane);
     rd = (lane < n) ? (hz + gj + (bx.lhi - bx.llo) + gtl) : 0.0;
     rlo_b = bx.hasLo ? (z - bx.lo - bx.slo) : 0.0;
     rhi_b = bx.hasHi ? (bx.hi - z - bx.shi) : 0.0;
@@ -1534,7 +1633,7 @@ __global__ __launch_bounds__(64) void kin_ltv_kernel(KinLtvArgs A) {
             wave_sync();
             s.vc[lane] = (lane < NC) ? (cs.lhi - cs.llo) : 0.0;
             wave_sync();
-            const double gtl = gt_dot<N>(s, lane);  // s.vc is rewritten below before its next read
+            const double gtl = gt_dot<N>(gpl, lane);  // s.vc is rewritten below before its next read
             const double cmax = wave_max(lane < n ? fabs((bx.lhi - bx.llo) + gtl) : 0.0);
             if (__builtin_fma(Rbox, cmax, dl) / l1 < -A.detect_eps) {
               infeas = true;
@@ -1599,6 +1698,7 @@ __global__ __launch_bounds__(64) void kin_ltv_kernel(KinLtvArgs A) {
       const double islo_c = cs.hasLo ? rcp_nr(cs.slo) : 0.0, ishi_c = cs.hasHi ? rcp_nr(cs.shi) : 0.0;
       const double illo_b = bx.hasLo ? rcp_nr(bx.llo) : 0.0, ilhi_b = bx.hasHi ? rcp_nr(bx.lhi) : 0.0;
       const double illo_c = cs.hasLo ? rcp_nr(cs.llo) : 0.0, ilhi_c = cs.hasHi ? rcp_nr(cs.lhi) : 0.0;
+      const double dj = s.dinv[lane < n ? lane : 0];  // this factor's inverse pivot, for both passes' solves
       double sm = 0.0, pp1 = 0.0, pp2 = 0.0, pp3 = 0.0, pp4 = 0.0;
 #pragma unroll 1
       for (int pass = 0; pass < 2; ++pass) {
@@ -1621,15 +1721,15 @@ __global__ __launch_bounds__(64) void kin_ltv_kernel(KinLtvArgs A) {
         wave_sync();
         s.vc[lane] = (lane < NC) ? ec : 0.0;
         wave_sync();
-        const double gte = gt_dot<N>(s, lane);  // every lane: the partner lanes' chains
+        const double gte = gt_dot<N>(gpl, lane);  // every lane: the partner lanes' chains
         const double rhs = (lane < n) ? (-rd - eb - gte) : 0.0;
         VC_TSTAMP(t_sol0)
-        const double dz = chol_solve<N>(Mr, s, rhs, lane);
+        const double dz = chol_solve<N>(Mr, s, rhs, lane, dj);
         VC_TACC(T_SOLVE, t_sol0)
         wave_sync();
         s.vz[lane] = (lane < n) ? dz : 0.0;
         wave_sync();
-        const double dyc = grow_dot<N>(s, lane);
+        const double dyc = grow_dot<N>(gpl, lane);
         const double d1 = bx.hasLo ? dz + rlo_b : 0.0;
         // (-rclo is - wlo (dz + rlo)) and (-rchi is - whi (rhi - dz)), roundings as noted above
         const double d2 = bx.hasLo ? __builtin_fma(islo_b, -rclo_b, -(wlo_b * (dz + rlo_b))) : 0.0;
@@ -1742,7 +1842,7 @@ __global__ __launch_bounds__(64) void kin_ltv_kernel(KinLtvArgs A) {
       s.vz[lane] = (lane < n) ? zfix : 0.0;
       wave_sync();
       // fixed-variable part of each active row, and its free-part norm for rho
-      const double gfix = grow_dot<N>(s, lane);
+      const double gfix = grow_dot<N>(gpl, lane);
       double gn2 = 0.0;
       {
         const int r = lane < NC ? lane : 0;
@@ -1820,16 +1920,17 @@ __global__ __launch_bounds__(64) void kin_ltv_kernel(KinLtvArgs A) {
       const double bnd_al = alo_c ? cs.lo : cs.hi;
       double zp = 0.0, emax = 0.0;
       {
+        const double dj = s.dinv[lane < n ? lane : 0];  // this round's factor: one read for all its solves
         wave_sync();
         s.vc[lane] = (lane < NC) ? (nu_c - rho_c * bnd_c) : 0.0;
         wave_sync();
-        const double gtn = gt_dot<N>(s, lane);
+        const double gtn = gt_dot<N>(gpl, lane);
         const double rhs = (lane < n) ? (fixed ? zfix : (base - gtn)) : 0.0;
-        zp = chol_solve<N>(Mr, s, rhs, lane);
+        zp = chol_solve<N>(Mr, s, rhs, lane, dj);
         wave_sync();
         s.vz[lane] = (lane < n) ? zp : 0.0;
         wave_sync();
-        const double yr = grow_dot<N>(s, lane);
+        const double yr = grow_dot<N>(gpl, lane);
         double rr = al_act ? (yr - bnd_al) : 0.0;  // e(nu), the active rows' violation
         // stop when the violation is below 1e-14 scale and (KIN_NU_TOL) the multiplier step R e
         // below KIN_NU_TOL scale: rho_c reaches 1e10 on rows with a small free part, and a
@@ -1849,12 +1950,12 @@ __global__ __launch_bounds__(64) void kin_ltv_kernel(KinLtvArgs A) {
             wave_sync();
             s.vc[lane] = (lane < NC) ? pd : 0.0;
             wave_sync();
-            const double gtp = gt_dot<N>(s, lane);
-            const double zq = chol_solve<N>(Mr, s, (lane < n && !fixed) ? gtp : 0.0, lane);  // M^-1 G' p
+            const double gtp = gt_dot<N>(gpl, lane);
+            const double zq = chol_solve<N>(Mr, s, (lane < n && !fixed) ? gtp : 0.0, lane, dj);  // M^-1 G' p
             wave_sync();
             s.vz[lane] = (lane < n) ? zq : 0.0;
             wave_sync();
-            const double gq = grow_dot<N>(s, lane);
+            const double gq = grow_dot<N>(gpl, lane);
             const double q = al_act ? gq : 0.0;  // S p on the active rows
             const double pq = wave_sum(pd * q);
 #ifdef VC_TIMING
@@ -1879,9 +1980,9 @@ __global__ __launch_bounds__(64) void kin_ltv_kernel(KinLtvArgs A) {
       s.vz[lane] = (lane < n) ? zp : 0.0;
       s.vc[lane] = (lane < NC) ? nu_c : 0.0;
       wave_sync();
-      const double gtnu = gt_dot<N>(s, lane);
+      const double gtnu = gt_dot<N>(gpl, lane);
       const double grad = (lane < n) ? (h_dot<N>(s, lane) + gj + gtnu) : 0.0;
-      const double ypc = grow_dot<N>(s, lane);
+      const double ypc = grow_dot<N>(gpl, lane);
       // the true violation, not CG's recurrence -- and, with KIN_STAT_CHECK, the free variables'
       // stationarity (the solves are trusted to make it ~0; a factor gone inaccurate must not certify)
 #if KIN_STAT_CHECK
@@ -2031,7 +2132,7 @@ __global__ __launch_bounds__(64) void kin_ltv_kernel(KinLtvArgs A) {
   // (The 20-stage recursion on all six states, every lane the same ~25 flops, 15 LDS reads, a six-way
   // lane select and a store per stage, was 11.7 K cycles of every problem.)
   {
-    const double y = grow_dot<N>(s, lane);  // s.vz = z
+    const double y = grow_dot<N>(gpl, lane);  // s.vz = z
     // dv_k -> vc[k], ddelta_k -> vz[n + k], k = 0..N-1 (0 at k = 0, from lanes NC and NC + 1)
     const int slot = lane < N - 1 ? 64 + lane + 1
                                   : (lane < NC ? n + (lane - (N - 1)) + 1 : (lane == NC ? 64 : (lane == NC + 1 ? n : 127)));
@@ -2112,12 +2213,49 @@ __global__ __launch_bounds__(64) void kin_gdots_kernel(int B, const double* G, c
   for (int i = lane; i < NC * n; i += 64) s.G[i / n][i % n] = G[(size_t)b * NC * n + i];
   s.vz[lane] = lane < n ? vz[(size_t)b * n + lane] : 0.0;
   s.vc[lane] = lane < NC ? vc[(size_t)b * NC + lane] : 0.0;
+  const GPlan<N> gpl = gplan_make<N>(s, lane);  // as the solve kernel sets it up
   wave_sync();
-  out_grow[(size_t)b * 64 + lane] = grow_dot<N>(s, lane);
-  out_gt[(size_t)b * 64 + lane] = gt_dot<N>(s, lane);
+  out_grow[(size_t)b * 64 + lane] = grow_dot<N>(gpl, lane);
+  out_gt[(size_t)b * 64 + lane] = gt_dot<N>(gpl, lane);
+}
+
+// Test hook (vc_debug_kin_trisolve): chol_solve as the solver calls it, on a factor the caller gives --
+// L[B][n][n], dinv[B][n], b[B][64] -- all 64 lanes of its result to out[B][64].  Lane j's row registers
+// take row j of L whole (the caller decides what lies on and above the diagonal; lanes >= n, which own
+// no row, get NaN), the LDS columns take the entries on and below the diagonal through lc_base.
+template <int N>
+__global__ __launch_bounds__(64) void kin_trisolve_kernel(int B, const double* L, const double* dinv,
+                                                          const double* rhs, double* out) {
+  constexpr int n = Dims<N>::n;
+  __shared__ Smem<N> s;
+  const int lane = threadIdx.x;
+  const int b = blockIdx.x;
+  if (b >= B) return;
+  const double* Lb = L + (size_t)b * n * n;
+  for (int i = lane; i < Smem<N>::LC_ZERO + 1; i += 64) s.Lc[i] = 0.0;
+  if (lane < 48) s.zrow[lane] = 0.0;
+  s.dinv[lane] = lane < n ? dinv[(size_t)b * n + lane] : 0.0;
+  wave_sync();
+  for (int i = lane; i < n * n; i += 64) {
+    const int j = i / n, k = i % n;
+    if (j >= k) s.Lc[lc_base<n>(k) + j] = Lb[i];
+  }
+  RowRegs<N> Lr;
+#pragma unroll
+  for (int k = 0; k < n; ++k) row_put<N>(Lr, k, lane < n ? Lb[lane * n + k] : __builtin_nan(""));
+  wave_sync();
+  out[(size_t)b * 64 + lane] = chol_solve<N>(Lr, s, rhs[(size_t)b * 64 + lane], lane);
 }
 
 // ---- host launcher ---------------------------------------------------------------
+hipError_t launch_kin_trisolve(int B, int N, const double* L, const double* dinv, const double* rhs, double* out,
+                               hipStream_t stream) {
+  if (B <= 0) return hipSuccess;
+  if (N != 20) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(kin_trisolve_kernel<20>, dim3(B), dim3(64), 0, stream, B, L, dinv, rhs, out);
+  return hipGetLastError();
+}
+
 hipError_t launch_kin_gdots(int B, int N, const double* G, const double* vz, const double* vc, double* out_grow,
                             double* out_gt, hipStream_t stream) {
   if (B <= 0) return hipSuccess;

@@ -360,6 +360,9 @@ hipError_t launch_rcp_probe(int n, const double* x, double* out, hipStream_t st)
 // Test hook (vc_debug_kin_gdots): kin_ltv.hip's two G products on given operands, N = 20 only.
 hipError_t launch_kin_gdots(int B, int N, const double* G, const double* vz, const double* vc, double* out_grow,
                             double* out_gt, hipStream_t stream);
+// Test hook (vc_debug_kin_trisolve): kin_ltv.hip's chol_solve on a given factor and right-hand side, N = 20 only.
+hipError_t launch_kin_trisolve(int B, int N, const double* L, const double* dinv, const double* rhs, double* out,
+                               hipStream_t stream);
 // Test hook (vc_debug_qp_fault): overwrite problem b's QP output with NaN, status VC_NONFINITE.
 hipError_t launch_kin_qp_fault(const KinLtvArgs& a, int N, int b, hipStream_t stream);
 bool kin_ric_built(int N);

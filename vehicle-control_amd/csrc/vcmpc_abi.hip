@@ -833,6 +833,26 @@ int vc_debug_kin_gdots(vc_ctx* c, int B, const void* G, const void* vz, const vo
   return st.finish();
 }
 
+int vc_debug_kin_trisolve(vc_ctx* c, int B, const void* L, const void* dinv, const void* b, void* out, int flags) {
+  if (int r = check_common(c, B, flags)) return r;
+  if (c->model != VC_MODEL_KINEMATIC || c->dtype != VC_F64 || vc::kin_ltv_smem_bytes(c->N) == 0)
+    return fail(c, VC_E_UNSUPPORTED, "vc_debug_kin_trisolve: kinematic fp64 contexts with the fused kernel's N only");
+  if (!L || !dinv || !b || !out) return fail(c, VC_E_ARG, "null pointer");
+  if (B == 0) return 0;
+  const int N = c->N, n = 2 * N;
+  Ptr dL, dd, db, dout;
+  Staging st(c, flags);
+  if (int r = st.bind([&] {
+        dL = st.in(L, (size_t)B * n * n * 8);
+        dd = st.in(dinv, (size_t)B * n * 8);
+        db = st.in(b, (size_t)B * 64 * 8);
+        dout = st.out(out, (size_t)B * 64 * 8);
+      }))
+    return r;
+  VC_HIP(c, vc::launch_kin_trisolve(B, N, dL, dd, db, dout, c->stream));
+  return st.finish();
+}
+
 int vc_debug_qp_fault(vc_ctx* c, int sqp_iter, int problem) {
   if (!c) return VC_E_ARG;
   c->fault_iter = sqp_iter;

@@ -113,6 +113,7 @@ PROTOTYPES = {
     "vc_debug_kin_merit": (C.c_int, [_vp, C.c_int] + [_vp] * 11 + [C.c_int, C.c_int, _vp, _vp, C.c_int]),
     "vc_debug_rcp": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int]),
     "vc_debug_kin_gdots": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int]),
+    "vc_debug_kin_trisolve": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int]),
     "vc_rollout": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int]),
     "vc_linearize": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int]),
     "vc_condense": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int]),

@@ -353,6 +353,17 @@ class Context:
                                                 flags))
         return u0, x, u, status, iters, diag
 
+    def debug_kin_trisolve(self, L, dinv, b):
+        """``vc_debug_kin_trisolve`` (test hook, kinematic fp64, N = 20): the fused kernel's
+        triangular solves (``chol_solve``) on the factor ``L[B, 2N, 2N]`` (whole rows, the entries on
+        and above the diagonal as given), the inverse pivots ``dinv[B, 2N]`` and the right-hand
+        sides ``b[B, 64]``.  Returns all 64 lanes of the result, ``[B, 64]``."""
+        B, n, f = self._batch(L), 2 * self.N, np.float64
+        out = self._like(L, (B, 64))
+        ptrs, flags = self._marshal([L, dinv, b, out], [(B, n, n), (B, n), (B, 64), (B, 64)], [f] * 4)
+        self._check(self.lib.vc_debug_kin_trisolve(self._h, B, *ptrs, flags))
+        return out
+
     def rollout(self, x0, ubar, kappa, ds):
         B, N, nx, f = self._batch(x0), self.N, self.nx, _NP_DT[self.dtype]
         xbar = self._like(x0, (B, N + 1, nx))
