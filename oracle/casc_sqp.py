@@ -248,41 +248,43 @@ def casc_qp(x0, ubar, kappa, ds, p, W, tyre="fiala"):
     gram.flush(Hm)
     Hm[:] += 2.0 * W["prox"] * eye
 
-    rows, rhs = [], []
+    rows, rhs, names = [], [], []
 
-    def add(row, r):
+    def add(row, r, family, k):
         rows.append(np.broadcast_to(row, (B, n))); rhs.append(np.broadcast_to(r, (B,)))
+        names.append((family, k))   # the row's family and stage (oracle/families.py)
 
     tw, tf = W["trust_w"], W["trust_Fx"]
     for k in range(N):
         if k >= 1:
-            add(-Gs[:, k, IUX], xs[:, k, IUX] - W["Ux_min"])
-            add(Gs[:, k, ID], W["delta_max"] - xs[:, k, ID])
-            add(-Gs[:, k, ID], xs[:, k, ID] - W["delta_min"])
+            add(-Gs[:, k, IUX], xs[:, k, IUX] - W["Ux_min"], "Ux_min", k)
+            add(Gs[:, k, ID], W["delta_max"] - xs[:, k, ID], "delta_max", k)
+            add(-Gs[:, k, ID], xs[:, k, ID] - W["delta_min"], "delta_min", k)
         for name in ("peng", "tyre_f_up", "tyre_f_lo", "tyre_r_up", "tyre_r_lo"):
             v, gr = T[name]
-            add(lin_row(gr, k) / S, -v[:, k] / S)
+            add(lin_row(gr, k) / S, -v[:, k] / S, name, k)
         up, dn = W["w_max"] - ubar[:, k, 1], ubar[:, k, 1] - W["w_min"]
         if tw > 0:
             up, dn = np.minimum(up, tw), np.minimum(dn, tw)
-        add(eye[2 * k + 1], up)
-        add(-eye[2 * k + 1], dn)
+        add(eye[2 * k + 1], up, "w_up", k)
+        add(-eye[2 * k + 1], dn, "w_dn", k)
         if tf > 0:
-            add(eye[2 * k], tf / S)
-            add(-eye[2 * k], tf / S)
+            add(eye[2 * k], tf / S, "trust_Fx_up", k)
+            add(-eye[2 * k], tf / S, "trust_Fx_dn", k)
     for m in range(Mh):
         j = N + m
         V = xp[:, m, PV]
-        add(-Gp[:, m, PV], V - W["V_min"])
+        add(-Gp[:, m, PV], V - W["V_min"], "V_min", j)
         # Fx - Peng / V <= 0, divided by S
-        add((p["Peng"] / V ** 2)[:, None] * Gp[:, m, PV] / S + eye[2 * j], -(ubar[:, j, 0] - p["Peng"] / V) / S)
+        add((p["Peng"] / V ** 2)[:, None] * Gp[:, m, PV] / S + eye[2 * j], -(ubar[:, j, 0] - p["Peng"] / V) / S,
+            "peng_pm", j)
         if tf > 0:
-            for c in (0, 1):
-                add(eye[2 * j + c], tf / S)
-                add(-eye[2 * j + c], tf / S)
+            for c, f in ((0, "trust_Fx"), (1, "trust_Fy")):
+                add(eye[2 * j + c], tf / S, f + "_up", j)
+                add(-eye[2 * j + c], tf / S, f + "_dn", j)
     C = np.stack(rows, axis=1)
     d = np.stack(rhs, axis=1)
-    return dict(xs=xs, xp=xp, Gs=Gs, Gp=Gp, H=Hm, g=g, C=C, d=d)
+    return dict(xs=xs, xp=xp, Gs=Gs, Gp=Gp, H=Hm, g=g, C=C, d=d, rows=names)
 
 
 def casc_sqp_solve(x0, ubar, kappa, ds, p, W, tyre="fiala", keep_qps=False, **qp_kw):
@@ -306,7 +308,8 @@ def casc_sqp_solve(x0, ubar, kappa, ds, p, W, tyre="fiala", keep_qps=False, **qp
         if it_sqp > 0:
             stopped |= ~np.asarray(sol["converged"], bool)
         z = np.where(stopped[:, None], 0.0, sol["z"])
-        rec = dict(ubar=u.copy(), dz=z, kkt=sol["kkt"], polished=sol["polished"], iters=sol["iters"])
+        rec = dict(ubar=u.copy(), dz=z, lam=sol["lam"], kkt=sol["kkt"], polished=sol["polished"], iters=sol["iters"],
+                   rows=Q["rows"], slack=Q["d"] - np.einsum("bmn,bn->bm", Q["C"], sol["z"]))
         if keep_qps:
             rec.update({k: Q[k] for k in ("H", "g", "C", "d", "Gs", "Gp")})
         du = z.reshape(B, H_, 2) * scale

@@ -260,31 +260,32 @@ def dyn_qp(x0, ubar, kappa, ds, p, W, tyre="linear"):
     gram.flush(H)
     H += 2.0 * W["prox"] * eye
 
-    rows, rhs = [], []
+    rows, rhs, names = [], [], []
 
-    def add(row, r):
+    def add(row, r, family, k):
         rows.append(np.broadcast_to(row, (B, n))); rhs.append(np.broadcast_to(r, (B,)))
+        names.append((family, k))   # the row's family and stage (oracle/families.py)
 
     tw, tf = W["trust_w"], W["trust_Fx"]
     for k in range(N):
         if k >= 1:
-            add(-G[:, k, IUX], xbar[:, k, IUX] - W["Ux_min"])
-            add(G[:, k, ID], W["delta_max"] - xbar[:, k, ID])
-            add(-G[:, k, ID], xbar[:, k, ID] - W["delta_min"])
+            add(-G[:, k, IUX], xbar[:, k, IUX] - W["Ux_min"], "Ux_min", k)
+            add(G[:, k, ID], W["delta_max"] - xbar[:, k, ID], "delta_max", k)
+            add(-G[:, k, ID], xbar[:, k, ID] - W["delta_min"], "delta_min", k)
         for name in ("peng", "tyre_f_up", "tyre_f_lo", "tyre_r_up", "tyre_r_lo"):
             v, gr = T[name]
-            add(lin_row(gr, k) / S, -v[:, k] / S)
+            add(lin_row(gr, k) / S, -v[:, k] / S, name, k)
         up, dn = W["w_max"] - ubar[:, k, IW], ubar[:, k, IW] - W["w_min"]
         if tw > 0:
             up, dn = np.minimum(up, tw), np.minimum(dn, tw)
-        add(eye[2 * k + 1], up)
-        add(-eye[2 * k + 1], dn)
+        add(eye[2 * k + 1], up, "w_up", k)
+        add(-eye[2 * k + 1], dn, "w_dn", k)
         if tf > 0:
-            add(eye[2 * k], tf / S)
-            add(-eye[2 * k], tf / S)
+            add(eye[2 * k], tf / S, "trust_Fx_up", k)
+            add(-eye[2 * k], tf / S, "trust_Fx_dn", k)
     C = np.stack(rows, axis=1)
     d = np.stack(rhs, axis=1)
-    return dict(xbar=xbar, A=A, Bm=Bm, G=G, H=H, g=g, C=C, d=d, terms=T)
+    return dict(xbar=xbar, A=A, Bm=Bm, G=G, H=H, g=g, C=C, d=d, terms=T, rows=names)
 
 
 def dyn_sqp_solve(x0, ubar, kappa, ds, p, W, tyre="linear", keep_qps=False, **qp_kw):
@@ -310,6 +311,8 @@ def dyn_sqp_solve(x0, ubar, kappa, ds, p, W, tyre="linear", keep_qps=False, **qp
                    iters=sol["iters"])
         if keep_qps:
             rec.update({k: Q[k] for k in ("xbar", "A", "Bm", "G", "H", "g", "C", "d")})
+        rec["rows"] = Q["rows"]
+        rec["slack"] = Q["d"] - np.einsum("bmn,bn->bm", Q["C"], sol["z"])
         du = dz.reshape(B, N, 2) * np.array([S, 1.0])
         alpha = domain_step(np.asarray(x0, np.float64), u, du, np.asarray(kappa, np.float64),
                             np.asarray(ds, np.float64), p, tyre, dyn_predict)

@@ -168,24 +168,24 @@ def kin_qp(x0, ubar, kappa, ds, L, W, x_ws=None):
     H += 2.0 * W["prox"] * np.eye(n)
 
     # inequalities C dz <= d
-    rows, rhs = [], []
+    rows, rhs, names = [], [], []   # names: every row's family and stage (oracle/families.py)
     I = np.eye(n)
     tr = {IA: W.get("trust_a", 0.0), IW: W.get("trust_w", 0.0)}
     for k in range(N):
-        for j, (lo, hi) in ((IA, (W["a_min"], W["a_max"])), (IW, (W["w_min"], W["w_max"]))):
+        for j, f, (lo, hi) in ((IA, "a", (W["a_min"], W["a_max"])), (IW, "w", (W["w_min"], W["w_max"]))):
             e = np.broadcast_to(I[2 * k + j], (B, n))
             up, dn = hi - ubar[:, k, j], ubar[:, k, j] - lo
             if tr[j] > 0:  # trust region |du| <= tr (SQP globalisation; 0 = off)
                 up, dn = np.minimum(up, tr[j]), np.minimum(dn, tr[j])
-            rows.append(e); rhs.append(up)
-            rows.append(-e); rhs.append(dn)
+            rows.append(e); rhs.append(up); names.append((f + "_up", k))
+            rows.append(-e); rhs.append(dn); names.append((f + "_dn", k))
     for k in range(1, N):
-        rows.append(-G[:, k, IV]); rhs.append(xv[:, k, IV] - W["v_min"])
-        rows.append(G[:, k, ID]); rhs.append(W["delta_max"] - xv[:, k, ID])
-        rows.append(-G[:, k, ID]); rhs.append(xv[:, k, ID] - W["delta_min"])
+        rows.append(-G[:, k, IV]); rhs.append(xv[:, k, IV] - W["v_min"]); names.append(("v_min", k))
+        rows.append(G[:, k, ID]); rhs.append(W["delta_max"] - xv[:, k, ID]); names.append(("delta_max", k))
+        rows.append(-G[:, k, ID]); rhs.append(xv[:, k, ID] - W["delta_min"]); names.append(("delta_min", k))
     C = np.stack(rows, axis=1)
     d = np.stack(rhs, axis=1)
-    return dict(xbar=xbar, e=eo, A=A, Bm=Bm, G=G, H=H, g=g, C=C, d=d)
+    return dict(xbar=xbar, e=eo, A=A, Bm=Bm, G=G, H=H, g=g, C=C, d=d, rows=names)
 
 
 def elastic_qp(H, g, C, d, ne, rho, eps_t=ELASTIC_EPS_T):

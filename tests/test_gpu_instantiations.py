@@ -27,6 +27,9 @@ with a sibling that is).  Coverage table -- a new template axis gets a row here 
     kin_ric     N = 10 .. 60, DET off / on          test_gpu_kin_ric.py, test_gpu_infeasible.py
     drive / horizon kernels, every model            test_gpu_closed_loop.py, test_gpu_sim_bookkeeping.py
 
+The template axes are one half; the other is which inequality rows bind on a test's problems -- the kernel x row
+family table heads tests/test_gpu_row_families.py.
+
 Bars (the project's own): single track 1e-5 on u* (Fx in N, w in rad/s) and 1e-6 on x*; cascaded 1e-5
 on u* in the scaled variable (Fx / 1000, w, Fy / 1000) and 1e-6 on x*.
 

@@ -1190,7 +1190,9 @@ __global__ __launch_bounds__(NTH, 1) void dyn_sqp_kernel(DynSqpArgs A) {
             }
           }
           rlast = block_max(s, rmax, wv, lane, 0);
-          if (rlast <= eps_r) break;
+          // stop on the rows' own O(1) scale, not on dscale (Ux - Ux_min ~ 10 there): 5e-6 left on a delta
+          // row is 2e-4 in the neighbouring w (ds / Ux = 0.03 s); the certificate below keeps eps_r
+          if (rlast <= 5.0e-7f) break;
         }
         // certificate
         float bad = 0.f;
