@@ -37,7 +37,7 @@ def rsign(x):
 # ----------------------------------------------------------------------------
 def euler_step(f, x, u, kappa, h):
     """x+ = x + h*f(x,u,k)  -- utils/integrators.py:15-23 (Euler)."""
-    h = np.asarray(h, dtype=np.float64)[..., None]
+    h = np.asarray(h)[..., None]
     return x + h * f(x, u, kappa)
 
 
@@ -61,7 +61,7 @@ def kin_temporal_ode(x, u, kappa, L):
     """Temporal ODE -- models/kinematic_car.py:34-41."""
     v, delta, s, ey, epsi, t = np.moveaxis(x, -1, 0)
     a, w = np.moveaxis(u, -1, 0)
-    kappa = np.asarray(kappa, dtype=np.float64)
+    kappa = np.asarray(kappa)
     s_dot = (v * np.cos(epsi)) / (1.0 - ey * kappa)
     ey_dot = v * np.sin(epsi)
     epsi_dot = v * (np.tan(delta) / L) - s_dot * kappa
@@ -76,7 +76,7 @@ def kin_spatial_ode(x, u, kappa, L):
     f' = [q a, q w, 1, rho tan(epsi), (tan(delta)/L) rho/cos(epsi) - kappa, q]."""
     v, delta, s, ey, epsi, t = np.moveaxis(x, -1, 0)
     a, w = np.moveaxis(u, -1, 0)
-    kappa = np.asarray(kappa, dtype=np.float64)
+    kappa = np.asarray(kappa)
     rho = 1.0 - ey * kappa
     c = np.cos(epsi)
     q = rho / (v * c)

@@ -26,6 +26,14 @@ with a sibling that is).  Coverage table -- a new template axis gets a row here 
     kin_ltv     N = 20                              test_gpu_parity.py (golden vectors)
     kin_ric     N = 10 .. 60, DET off / on          test_gpu_kin_ric.py, test_gpu_infeasible.py
     drive / horizon kernels, every model            test_gpu_closed_loop.py, test_gpu_sim_bookkeeping.py
+    models.hip  ode / plant_step / spatial_step,    test_gpu_models.py::test_kin_points_vs_oracle[f64 / f32],
+                KIN_NX / DYN_NX, f64 / f32,         test_dyn_points_vs_oracle[linear / fiala - f64 / f32]
+                linear / fiala
+    models.hip  rollout, KIN_NX / DYN_NX,           test_gpu_models.py::test_kin_rollout_vs_oracle[f64 / f32],
+                f64 / f32, linear / fiala           test_dyn_rollout_vs_oracle[linear / fiala - f64 / f32]
+    models.hip  kin_linearize (f64 only)            test_gpu_models.py::test_kin_rollout_vs_oracle[f64]
+    models.hip  DYN_NX kernels, cascaded context    test_gpu_models.py::test_cascaded_context_is_the_dynamic_model
+                                                    (the kernel x NX x dtype x tyre table heads that file)
 
 The template axes are one half; the other is which inequality rows bind on a test's problems -- the kernel x row
 family table heads tests/test_gpu_row_families.py.

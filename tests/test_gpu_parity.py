@@ -1,5 +1,7 @@
-"""GPU parity: every HIP entry point, called through the C ABI (libvcmpc.so),
-against the CPU oracle and the committed golden vectors.
+"""GPU parity: the HIP entry points, called through the C ABI (libvcmpc.so) on fp64 contexts,
+against the CPU oracle and the committed golden vectors.  The model entry points (vc_ode, vc_plant_step,
+vc_spatial_step, vc_rollout, vc_linearize) are checked here in fp64 only, the dynamic ones on the recorded
+Fiala rows; their fp32, linear-tyre, dynamic-rollout and cascaded-context rows are in tests/test_gpu_models.py.
 
 Tolerances (written here, per the north star): u* to ||u* - u*_ref||_inf < 1e-5
 (the BASELINE.json contract); model steps / rollout / Jacobians / condensed QP
